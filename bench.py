@@ -1,12 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- RPBCAC training throughput on MI355X (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-`python bench.py --gpus N` with N > 1 and no launcher around it starts the N ranks itself (it re-executes
-under torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1); a mismatch between --gpus and the
-ranks that actually joined aborts -- the line never reports a GPU count it did not run on.
+`python bench.py --gpus N` with N > 1 and no launcher around it starts the N ranks itself (it runs
+torch.distributed.run as a child process, one process per GPU, rendezvous on 127.0.0.1); a mismatch between --gpus
+and the ranks that actually joined aborts -- the line never reports a GPU count it did not run on.
 
 One "step" = one training block of the reference loop (training/train_agents.py:
 46-163): n_ep_fixed=50 episodes x max_ep_len=20 environment steps of rollout for
@@ -16,10 +16,16 @@ skipped inside the timed region.  Data: synthetic (random goals, Glorot-init
 networks, on-device grid-world); arithmetic fp32 like the reference.
 
 Prints ONE JSON line (rank 0): metric = agent-steps/s (whole loop), plus
-consensus-updates/s, the per-kernel breakdown, `roofline` for the dominant
-kernel, `roofline_consensus` for the consensus kernel, `cpu_baseline`, and (N=1) `extra`: short runs of the
-other workloads in the same process, among them the north-star target shape whose consensus-kernel roofline is
+consensus-updates/s.  A plain run does only that: set-up, W warm-up blocks, K timed blocks, the line.
+With --full the line also carries the per-kernel breakdown (HIP events on the launches of two timed steps), `roofline`
+for the dominant kernel, `roofline_consensus` for the consensus kernel, the phase split (one more, synchronised
+block), `cpu_baseline`, and (N=1) `extra`: short runs of the other workloads in the same process, among them the
+headline in its exact operand form and the north-star target shape whose consensus-kernel roofline is
 `roofline_consensus_target`.
+
+--dump-outputs DIR writes, after the timed blocks, what the last timed block computed (dump_outputs()): its
+per-episode return logs and a fixed, seeded sample of the trained network weights, as DIR/<name>.npy.  Seeds,
+goals and initial weights are fixed, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -269,7 +275,7 @@ def _free_port():
 
 def _self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves
-    (one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1) and become that launcher.
+    (one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1) in a child process and exit with its status.
     The reference has no counterpart -- it runs one SGE job per seed (.../seed=100/job.sh:4)."""
     if not args.stub_engine:
         have = torch.cuda.device_count()
@@ -282,7 +288,9 @@ def _self_launch(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # RCCL needs dmabuf IPC on this driver
     env.setdefault("OMP_NUM_THREADS", "8")
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    # a child process, not exec: device_count() above may already have opened the GPU runtime in this one
+    import subprocess
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def parse_args(argv=None):
@@ -292,13 +300,18 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="cfg4_shard", choices=sorted(WORKLOADS))
     ap.add_argument("--seeds-per-gpu", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event times and rooflines, the phase "
+                         "split, the other workloads (`extra`, with the headline's exact operand form) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: no per-kernel HIP events")
     ap.add_argument("--kernel-timing-steps", type=int, default=2,
                     help="timed steps whose launches carry HIP events (evenly spaced; 0 = all of them).  Two events per launch cost "
                          "~10 us of queue time each: on all ~5000 launches of a 10-step run that is 5 %% of the step "
                          "(204.4 against 194.4 ms per block at cfg4_shard, profiles/r04x_event_overhead.txt)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other workloads (`extra`)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the short runs of the other workloads (`extra`)")
     ap.add_argument("--stub-engine", action="store_true", help="TEST ONLY: CPU stub engine + gloo, exercises the launcher/"
                     "barrier/all-reduce control path without a GPU")
     return ap.parse_args(argv)
@@ -313,7 +326,7 @@ def timed_steps(steps, k):
 
 def time_blocks(eng, steps, warmup, barrier, S, dev, tlib=None, want_kernels=True, event_steps=0):
     """W untimed blocks, then exactly K timed blocks bracketed by barrier + synchronize; returns
-    (seconds on this rank, mean return curve over ALL ranks' seeds).  Per-kernel HIP events ride on the launches of
+    (seconds on this rank, mean return curve over ALL ranks' seeds, the last timed block's (team, adv, est) logs).  Per-kernel HIP events ride on the launches of
     timed_steps(steps, event_steps) -- inside the timed region, on the launch stream."""
     from rcmarl_amd.parallel import allreduce_curves
     for _ in range(warmup):
@@ -335,7 +348,32 @@ def time_blocks(eng, steps, warmup, barrier, S, dev, tlib=None, want_kernels=Tru
     dt = time.perf_counter() - t0
     if tlib is not None:
         tlib.enabled = False
-    return dt, curve
+    return dt, curve, (team, adv, est)
+
+
+DUMP_BYTES = 56 << 20         # weight samples of --dump-outputs; the return logs are a few kB (64 MB in all at most)
+
+
+def dump_outputs(eng, last, out_dir):
+    """What the last timed block handed its caller, as out_dir/<name>.npy: the per-episode logs run_block() returned
+    (team_returns / adv_returns / est_returns, float64 [E, S]) and the network weights it trained (theta_<net>, float32
+    [rows, P]: one row per (seed, agent), padding dropped).  Where a network's rows exceed its share of DUMP_BYTES, a fixed
+    seeded sample of whole rows is written; theta_<net>_rows holds their flat seed * N + agent indices (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in zip(("team_returns", "adv_returns", "est_returns"), last):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    nets = [k for k in ("actor", "critic", "tr", "critic_local") if k in eng.theta]
+    sizes = getattr(eng, "P", {})
+    for net in nets:
+        th = eng.theta[net]
+        rows = th.reshape(-1, th.shape[-1])
+        P = sizes.get(net.replace("_local", ""), rows.shape[1])
+        n = rows.shape[0]
+        k = max(1, min(n, DUMP_BYTES // len(nets) // (4 * P)))
+        idx = np.arange(n) if k == n else np.sort(np.random.default_rng(12345).choice(n, size=k, replace=False))
+        sample = rows[torch.as_tensor(idx, device=rows.device)][:, :P]
+        np.save(os.path.join(out_dir, "theta_%s.npy" % net), sample.detach().float().cpu().numpy())
+        np.save(os.path.join(out_dir, "theta_%s_rows.npy" % net), idx.astype(np.float64))
 
 
 def _self_hash():
@@ -398,7 +436,7 @@ def extra_workloads(main_name, tlib, barrier, dev, main_steps=2, main_warmup=1, 
             # single instances are launch-bound: timed WITHOUT the per-launch events, so the engine's captured epochs
             # (hipGraph, engine._epoch) run as they do for a user of the drop-in path
             single = name.endswith("_single")
-            dt, _ = time_blocks(eng, steps, warm, barrier, S, dev, tlib, want_kernels=not single, event_steps=1)
+            dt, _, _ = time_blocks(eng, steps, warm, barrier, S, dev, tlib, want_kernels=not single, event_steps=1)
             ksum = {} if single else tlib.summary()
             finite = all(bool(torch.isfinite(eng.theta[k]).all().item()) for k in ("actor", "critic", "tr"))
             c = eng.cfg
@@ -460,6 +498,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         _self_launch(args)                                       # does not return
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -513,17 +553,24 @@ def main(argv=None):
         if not stub:
             torch.cuda.synchronize()
 
-    dt, curve = time_blocks(eng, args.steps, args.warmup, barrier, S, dev, tlib, want_kernels=not args.no_kernel_timing,
-                            event_steps=args.kernel_timing_steps)
+    # per-kernel HIP events only under --full: a plain run's timed steps carry nothing the headline does not need
+    dt, curve, last = time_blocks(eng, args.steps, args.warmup, barrier, S, dev, tlib,
+                                  want_kernels=args.full and not args.no_kernel_timing, event_steps=args.kernel_timing_steps)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if use_pg:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)                # the slowest rank's clock
     dt = float(tmax.item())
     B_steady = eng.cap
+    if args.dump_outputs:
+        # before anything else runs a block: the weights are those of the last timed step
+        if one_instance and use_pg:
+            eng.sync_shards()                                      # a collective: every rank takes part, rank 0 writes
+        if rank == 0:
+            dump_outputs(eng, last, args.dump_outputs)
 
-    ksum = tlib.summary() if tlib is not None else {}              # per-kernel HIP-event times of the timed region
+    ksum = tlib.summary() if tlib is not None and args.full else {}   # per-kernel HIP-event times of the timed region
     roof = rooflines(tlib, ksum, args.workload) if ksum else None  # (before the extras reset the counters)
-    ph = phase_split(eng)
+    ph = phase_split(eng) if args.full else None
 
     finite = all(bool(torch.isfinite(eng.theta[k]).all().item()) for k in ("actor", "critic", "tr"))
     if use_pg:
@@ -540,7 +587,7 @@ def main(argv=None):
         env_steps = c.n_ep_fixed * c.max_ep_len
         agent_steps = jobs * S * N * env_steps * args.steps
         cons_updates = jobs * S * eng.n_coop * c.n_epochs * args.steps
-        ph_total = ph["rollout"] + ph["phase1"] + ph["phase2"] + ph["phase3"]
+        ph_total = ph["rollout"] + ph["phase1"] + ph["phase2"] + ph["phase3"] if ph else 0.0
         out = {
             "metric": "agent-steps/sec (whole RPBCAC training loop; + consensus-updates/sec)",
             "value": agent_steps / dt, "unit": "agent-steps/s", "n_gpus": world, "steps": args.steps,
@@ -552,7 +599,7 @@ def main(argv=None):
                           "operands as two f16 pieces (the value to one unit in its last place: 22-23 significand bits where fp32 has 24; "
                           "RCMARL_LAT_F16=3, the default; a value below 2^-3 of its fixed scale -- |alpha W1| < 1.2e-4, |dz1| < 4.9e-4 -- is carried to an "
                           "absolute 3e-11 / 1.2e-10 instead) or, =0, as three bf16 pieces whose sum is the fp32 value bit for bit -- that form "
-                          "is timed in extra.<workload>_exact and reported as ms_per_step_exact / value_exact of this same line",
+                          "is timed (with --full) in extra.<workload>_exact and reported as ms_per_step_exact / value_exact of this same line",
             "data": "synthetic" if not stub else "STUB ENGINE (control-path test, not a measurement)",
             "config": {"workload": args.workload, "description": w["desc"], "n_agents": N, "seeds_per_gpu": S,
                        "grid": [w["nrow"], w["ncol"]], "H": w["H"], "d": w["d"], "replay_rows_B": B_steady, "fast_lr": c.fast_lr, "slow_lr": c.slow_lr, "weights_finite": finite,
@@ -562,11 +609,12 @@ def main(argv=None):
                                       "seed-sharded, %d seeds/GPU x %d GPU, one all-reduce of return curves" % (S, world)},
             "comm": comm,
             "consensus_updates_per_s": cons_updates / dt,
-            "consensus_updates_per_s_phase2_only": (S * eng.n_coop * c.n_epochs) / ph["phase2"] if ph["phase2"] > 0 else None,
-            "phase_seconds_per_block": {k: ph[k] for k in ("rollout", "phase1", "phase2", "phase3")},
-            "phase_fraction": {k: ph[k] / ph_total for k in ("rollout", "phase1", "phase2", "phase3")} if ph_total > 0 else None,
             "mean_team_return_last_block": float(curve[-c.n_ep_fixed:, 0].mean()),
         }
+        if ph:
+            out["consensus_updates_per_s_phase2_only"] = (S * eng.n_coop * c.n_epochs) / ph["phase2"] if ph["phase2"] > 0 else None
+            out["phase_seconds_per_block"] = {k: ph[k] for k in ("rollout", "phase1", "phase2", "phase3")}
+            out["phase_fraction"] = {k: ph[k] / ph_total for k in ("rollout", "phase1", "phase2", "phase3")} if ph_total > 0 else None
         if abs(c.fast_lr - 0.01) > 1e-12:
             out["deviation"] = {"fast_lr": c.fast_lr, "reference": 0.01,
                                 "why": "the reference's plain full-batch SGD local fit diverges to NaN at this input width "
@@ -580,14 +628,14 @@ def main(argv=None):
             out["kernel_timing"] = {"steps_with_events": timed_steps(args.steps, args.kernel_timing_steps), "of_timed_steps": args.steps,
                                     "what": "HIP events around every C-ABI launch of these timed steps, on the launch stream; "
                                             "launches / total_ms in `kernels` count those steps only"}
-        if world == 1 and not stub and not args.no_extra:
+        if args.full and world == 1 and not stub and not args.no_extra:
             del eng
             torch.cuda.empty_cache()
             out["extra"], k1t = extra_workloads(args.workload, tlib, barrier, dev, args.steps, args.warmup, cpu_target=not args.no_cpu_baseline)
             if k1t is not None:
                 out["roofline_consensus_target"] = k1t
         cache = os.path.join(ROOT, ".bench_cpu_baseline_%s.json" % args.workload.replace("cfg5_shard", "cfg5_1gpu"))
-        if not args.no_cpu_baseline and world == 1 and not stub:
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:
             try:
                 out["cpu_baseline"] = cpu_baseline(w)
                 out["speedup_vs_cpu_port"] = _speedup(out)
@@ -595,7 +643,7 @@ def main(argv=None):
                     json.dump(dict(out["cpu_baseline"], bench_py_sha=_self_hash(), workload=args.workload), f)
             except Exception as e:                                     # the baseline must never kill the bench line
                 out["cpu_baseline"] = {"error": repr(e)}
-        elif not args.no_cpu_baseline and not stub and os.path.exists(cache):
+        elif args.full and not args.no_cpu_baseline and not stub and os.path.exists(cache):
             # timed on rank 0 at N = 1 only (a few tens of CPU-seconds); the N > 1 lines of the same box carry that record
             try:
                 with open(cache) as f:
@@ -621,11 +669,12 @@ def main(argv=None):
                "roofline_consensus_target", "kernel_timing", "deviation", "phase_seconds_per_block", "phase_fraction", "comm")
         line = {k: out[k] for k in big if k in out}
         line.update({k: v for k, v in out.items() if k not in big and k not in ("roofline", "cpu_baseline")})
-        line["summary_ms_per_step"] = dict({args.workload: round(out["ms_per_step"], 2)},
-                                           **{k: (round(v["ms_per_step"], 2) if "ms_per_step" in v else "error")
-                                              for k, v in (out.get("extra") or {}).items()})
-        line["summary_hipgraph_epochs"] = {k: v.get("epochs_replayed_from_hipgraph") for k, v in (out.get("extra") or {}).items()
-                                           if "epochs_replayed_from_hipgraph" in v}
+        if args.full:
+            line["summary_ms_per_step"] = dict({args.workload: round(out["ms_per_step"], 2)},
+                                               **{k: (round(v["ms_per_step"], 2) if "ms_per_step" in v else "error")
+                                                  for k, v in (out.get("extra") or {}).items()})
+            line["summary_hipgraph_epochs"] = {k: v.get("epochs_replayed_from_hipgraph") for k, v in (out.get("extra") or {}).items()
+                                               if "epochs_replayed_from_hipgraph" in v}
         for k in ("roofline", "cpu_baseline"):
             if k in out:
                 line[k] = _brief(out[k])

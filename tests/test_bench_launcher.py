@@ -59,3 +59,27 @@ def test_more_gpus_than_visible_is_refused():
     have = torch.cuda.device_count()
     r = _run(["--gpus", str(have + 2), "--steps", "1", "--warmup", "0"])
     assert r.returncode != 0 and "GPU(s) visible" in (r.stderr + r.stdout)
+
+
+def test_plain_run_and_dump_outputs(tmp_path):
+    """A plain run prints the headline and nothing measured besides it; --dump-outputs writes what the last timed step
+    returned (float64 return logs, float32 weights) and --full adds the phase split."""
+    import numpy as np
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--stub-engine", "--workload", "cfg1_batched", "--seeds-per-gpu", "2",
+              "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _json_line(r.stdout)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] >= 10.0 and out["higher_is_better"] is True
+    assert out["unit"] == "agent-steps/s" and out["dtype"] == "f32"
+    for k in ("extra", "cpu_baseline", "kernels", "roofline", "phase_seconds_per_block", "summary_ms_per_step"):
+        assert k not in out, k
+    team = np.load(tmp_path / "out" / "team_returns.npy")
+    assert team.dtype == np.float64 and team.shape == (50, 2) and (team == [[-1000.0, -1001.0]]).all()
+    for net in ("actor", "critic", "tr"):
+        assert np.load(tmp_path / "out" / ("theta_%s.npy" % net)).dtype == np.float32
+    assert sum(f.stat().st_size for f in (tmp_path / "out").iterdir()) <= 64 << 20
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--stub-engine", "--workload", "cfg1_batched", "--seeds-per-gpu", "2",
+              "--full"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _json_line(r.stdout)
+    assert out["steps"] == 2 and "phase_seconds_per_block" in out
