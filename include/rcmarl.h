@@ -152,7 +152,7 @@ int rcmarl_mid_fit_lattice(const float* a1t, const float* theta, const float* y,
                            int dzp_kt, int S, int N, int B, int in_dim, int hid, int ldp, int ldb, int* ovf_flags, void* stream);
 
 /* (ABI 3: the fused local-fit prototypes -- rcmarl_fit_fused, rcmarl_forward_mid and their six helpers, ABI 2 -- left the library:
- * exact, measured not faster than the three launches above; tools/prototypes/fused_fit.hip keeps the source.) */
+ * exact, measured not faster than the three launches above; the shelved source was removed after commit a145e19.) */
 
 /* Shuffle permutations of the adversaries' mini-batch fits (Keras fit(shuffle=True) inside
  * agents/adversarial_CAC_agents.py:38-41,131-135,163-165,237-253).  TensorFlow's shuffle RNG is not reproducible

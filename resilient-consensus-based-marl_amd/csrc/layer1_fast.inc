@@ -113,11 +113,11 @@ struct RowsB {
 };
 
 // ---- the tile loop ---------------------------------------------------------------------------
-template <int MT, int NBUF, class LA, class LB>
+// One LDS buffer per operand; the next tile waits in registers (a double-buffered LDS form measured slower).
+template <int MT, class LA, class LB>
 __device__ __forceinline__ void mainloop(const LA& la, const LB& lb, int n_tiles, float* As, float* Bs,
                                          rc_f32x16 (&acc)[MT]) {
   constexpr int BM = 32 * MT;
-  constexpr int A_SZ = FBK * BM, B_SZ = FBN * FBS;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int half = lane >> 5, l31 = lane & 31;
 #pragma unroll
@@ -127,30 +127,14 @@ __device__ __forceinline__ void mainloop(const LA& la, const LB& lb, int n_tiles
   float4 ra[LA::PER], rb[LB::PER];
   la.fetch(0, ra);
   lb.fetch(0, rb);
-  if (NBUF == 2) {
+  for (int t = 0; t < n_tiles; ++t) {
+    __syncthreads();               // previous tile fully consumed
     la.commit(ra, As);
     lb.commit(rb, Bs);
-    if (n_tiles > 1) { la.fetch(FBK, ra); lb.fetch(FBK, rb); }
-  }
-  for (int t = 0; t < n_tiles; ++t) {
-    float* Ac = As + (NBUF == 2 ? (t & 1) * A_SZ : 0);
-    float* Bc = Bs + (NBUF == 2 ? (t & 1) * B_SZ : 0);
-    if (NBUF == 1) {
-      __syncthreads();               // previous tile fully consumed
-      la.commit(ra, Ac);
-      lb.commit(rb, Bc);
-      __syncthreads();
-      if (t + 1 < n_tiles) { la.fetch((t + 1) * FBK, ra); lb.fetch((t + 1) * FBK, rb); }
-    } else {
-      __syncthreads();               // tile t is in LDS; every wave is done with buffer (t+1)&1
-      if (t + 1 < n_tiles) {         // the registers hold tile t+1: park it in the other buffer, refill with t+2
-        la.commit(ra, As + ((t + 1) & 1) * A_SZ);
-        lb.commit(rb, Bs + ((t + 1) & 1) * B_SZ);
-        if (t + 2 < n_tiles) { la.fetch((t + 2) * FBK, ra); lb.fetch((t + 2) * FBK, rb); }
-      }
-    }
-    const float* arow = Ac + (4 * half) * BM + l31;                 // As[8g+4half+c][32mt+l31]
-    const float* brow = Bc + (wave * 32 + l31) * FBS + 4 * half;    // Bs[n][8g+4half .. +3]
+    __syncthreads();
+    if (t + 1 < n_tiles) { la.fetch((t + 1) * FBK, ra); lb.fetch((t + 1) * FBK, rb); }
+    const float* arow = As + (4 * half) * BM + l31;                 // As[8g+4half+c][32mt+l31]
+    const float* brow = Bs + (wave * 32 + l31) * FBS + 4 * half;    // Bs[n][8g+4half .. +3]
     float4 bq = ld4(brow);
     float af[2][MT];
 #pragma unroll
@@ -176,15 +160,14 @@ __device__ __forceinline__ void mainloop(const LA& la, const LB& lb, int n_tiles
 }
 
 // ---- forward: a1t[col][b] = lrelu(z + b1[col]) ------------------------------------------------
-template <int NBUF>
 __global__ __launch_bounds__(256, 3) void k_fwd(const float* __restrict__ x, long x_seed_stride,
                                              const float* __restrict__ theta, float* __restrict__ a1t, int N, int B,
                                              int in_dim, int ldp, int ldb) {
   constexpr int MT = 5, BM = 160;
   RCMARL_DYN_SMEM(float, smem);
   float* As = smem;
-  float* Bs = As + NBUF * FBK * BM;
-  float* bias = Bs + NBUF * FBN * FBS;                     // [BM]
+  float* Bs = As + FBK * BM;
+  float* bias = Bs + FBN * FBS;                            // [BM]
   const int s = blockIdx.z, m0 = blockIdx.y * BM, n0 = blockIdx.x * FBN;
   const int ncols = N * 20;
   const float* theta_s = theta + (long)s * N * ldp;
@@ -197,7 +180,7 @@ __global__ __launch_bounds__(256, 3) void k_fwd(const float* __restrict__ x, lon
   const FwdA<MT> la{theta_s, ldp, N, m0 / 20};
   const RowsB lb{x + (long)s * x_seed_stride, (long)in_dim, B, 0, n0, false};
   rc_f32x16 acc[MT];
-  mainloop<MT, NBUF>(la, lb, in_dim / FBK, As, Bs, acc);   // (its barriers publish bias[])
+  mainloop<MT>(la, lb, in_dim / FBK, As, Bs, acc);         // (its barriers publish bias[])
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = n0 + wave * 32 + (lane & 31);
   if (n < B) {
@@ -227,7 +210,7 @@ struct ApplyAdam {      // TF2 ResourceApplyAdam (see EpiAdam)
   }
 };
 
-template <int NBUF, class Apply>
+template <class Apply>
 __global__ __launch_bounds__(256) void k_bwd(const float* __restrict__ x, long x_seed_stride,
                                              const float* __restrict__ dz1t, float* __restrict__ theta,
                                              const int* __restrict__ mask, int N, int B, int in_dim, int ldp, int ldb,
@@ -235,13 +218,13 @@ __global__ __launch_bounds__(256) void k_bwd(const float* __restrict__ x, long x
   constexpr int MT = 4, BM = 128;
   RCMARL_DYN_SMEM(float, smem);
   float* As = smem;
-  float* Bs = As + NBUF * FBK * BM;
+  float* Bs = As + FBK * BM;
   const int s = blockIdx.z, m0 = blockIdx.y * BM, n0 = blockIdx.x * FBN;
   const int ncols = N * 20;
   const BwdA<MT> la{x + (long)s * x_seed_stride, in_dim, B, m0};
   const RowsB lb{dz1t + (long)s * ncols * ldb, (long)ldb, ncols, B, n0, true};
   rc_f32x16 acc[MT];
-  mainloop<MT, NBUF>(la, lb, (B + FBK - 1) / FBK, As, Bs, acc);
+  mainloop<MT>(la, lb, (B + FBK - 1) / FBK, As, Bs, acc);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = n0 + wave * 32 + (lane & 31);
   if (col < ncols) {
@@ -262,7 +245,7 @@ __global__ __launch_bounds__(256) void k_bwd(const float* __restrict__ x, long x
   }
 }
 
-inline size_t smem_fwd(int nbuf) { return sizeof(float) * ((size_t)nbuf * (FBK * 160 + FBN * FBS) + 160); }
-inline size_t smem_bwd(int nbuf) { return sizeof(float) * ((size_t)nbuf * (FBK * 128 + FBN * FBS)); }
+inline size_t smem_fwd() { return sizeof(float) * (FBK * 160 + FBN * FBS + 160); }
+inline size_t smem_bwd() { return sizeof(float) * (FBK * 128 + FBN * FBS); }
 
 }  // namespace fast

@@ -284,7 +284,7 @@ bool small_enabled() {
   return v != 0;
 }
 
-// 0 = generic kernels only, 1 = fast path (default).  (A double-buffered LDS form of the fast path measured slower.)
+// 0 = generic kernels only, 1 = fast path (default).
 // RCMARL_GEMM is a tuning/bisecting knob, read once.
 int gemm_variant() {
   static int v = -1;
@@ -330,8 +330,8 @@ RCMARL_EXPORT int rcmarl_layer1_forward(const float* x, long x_seed_stride, cons
   }
   if (var > 0 && hid == 20 && (in_dim % fast::FBK) == 0 && aligned16(x) && (x_seed_stride & 3) == 0) {
     const dim3 grid(rc_ceil_div(B, fast::FBN), rc_ceil_div(N * 20, 160), S), block(256);
-    const size_t smem = fast::smem_fwd(var);
-    RCMARL_LAUNCH((fast::k_fwd<1>), grid, block, smem, stream, x, x_seed_stride, theta, a1t, N, B, in_dim, ldp, ldb);
+    const size_t smem = fast::smem_fwd();
+    RCMARL_LAUNCH(fast::k_fwd, grid, block, smem, stream, x, x_seed_stride, theta, a1t, N, B, in_dim, ldp, ldb);
     return rcmarl_check_launch();
   }
   const dim3 grid(rc_ceil_div(B, BN), rc_ceil_div(N * hid, BM), S), block(256);
@@ -357,9 +357,9 @@ RCMARL_EXPORT int rcmarl_layer1_backward_sgd(const float* x, long x_seed_stride,
   }
   if (var > 0 && hid == 20 && (in_dim & 3) == 0 && aligned16(x) && (x_seed_stride & 3) == 0) {
     const dim3 grid(rc_ceil_div(N * 20, fast::FBN), rc_ceil_div(in_dim, 128), S), block(256);
-    const size_t smem = fast::smem_bwd(var);
+    const size_t smem = fast::smem_bwd();
     const fast::ApplySgd ap{lr};
-    RCMARL_LAUNCH((fast::k_bwd<1, fast::ApplySgd>), grid, block, smem, stream, x, x_seed_stride, dz1t, theta, mask, N, B,
+    RCMARL_LAUNCH((fast::k_bwd<fast::ApplySgd>), grid, block, smem, stream, x, x_seed_stride, dz1t, theta, mask, N, B,
                     in_dim, ldp, ldb, ap);
     return rcmarl_check_launch();
   }
@@ -377,9 +377,9 @@ RCMARL_EXPORT int rcmarl_layer1_backward_adam(const float* x, long x_seed_stride
   const int var = gemm_variant();
   if (var > 0 && hid == 20 && (in_dim & 3) == 0 && aligned16(x) && (x_seed_stride & 3) == 0) {
     const dim3 grid(rc_ceil_div(N * 20, fast::FBN), rc_ceil_div(in_dim, 128), S), block(256);
-    const size_t smem = fast::smem_bwd(var);
+    const size_t smem = fast::smem_bwd();
     const fast::ApplyAdam ap{adam_m, adam_v, alpha, one_m_b1, one_m_b2, eps};
-    RCMARL_LAUNCH((fast::k_bwd<1, fast::ApplyAdam>), grid, block, smem, stream, x, x_seed_stride, dz1t, theta, mask, N, B,
+    RCMARL_LAUNCH((fast::k_bwd<fast::ApplyAdam>), grid, block, smem, stream, x, x_seed_stride, dz1t, theta, mask, N, B,
                     in_dim, ldp, ldb, ap);
     return rcmarl_check_launch();
   }

@@ -12,26 +12,15 @@
 //   k_consensus_head  estimate consensus + projection residual                    (:168-206, :60-84)
 //   k_mid_actor       softmax / TD-weighted sparse CE forward+backward            (:86-101)
 //   k_small_sgd / k_small_adam / k_head_apply   reduce partials, apply updates
-// Round 6 (visit l): the 20-unit layers of this file run THREE of the four piece products (h x h, h x l, l x h); the low x low one is
-// at most 2^-22 of a term -- a quarter of an fp32 rounding step of it -- and leaving it out moves k_mid_fit_v8's gradient records by
-// 0.7-1.5e-7 of their scale, LESS than the fp32 vector-ALU form of the same kernel differs from the four-pass form through its
-// summation order alone (2.2e-7; profiles/r06l_mid_ab_drop_ll.txt), for 5 % of the kernel's time (434-440 -> 410-419 us).
-// -DRC_V8_DROP_LL=0 restores the fourth pass; the adversaries' mini-batch chain (minibatch_fit.hip) keeps all four.
-#ifndef RC_V8_DROP_LL
-#define RC_V8_DROP_LL 1
-#endif
 #include "rcmarl_lattice.h"
-// A/B switch: raise the wavefront's issue priority around its matrix-core groups (so that a group is issued as early as possible and the
-// other wavefronts' vector work runs under it).
-#ifndef RC_MID_SETPRIO
-#define RC_MID_SETPRIO 0
-#endif
-#define RC_MX_BEGIN() do { if (RC_MID_SETPRIO) rc_setprio(RC_MID_SETPRIO); } while (0)
-#define RC_MX_END() do { if (RC_MID_SETPRIO) rc_setprio(0); } while (0)
 #include <stdlib.h>
 #include "selnet_generated.inc"
 
 namespace {
+
+// The 20-unit layers of this file (k_mid_fit_v8, k_consensus_head_mx, k_mid_value_mx) run THREE of the four piece products: the
+// low x low one is left out (v8_mfma, rcmarl_lattice.h).
+constexpr bool kMidDropLL = true;
 
 constexpr int ROWS = 256;          // replay rows per workgroup
 constexpr int LDR = ROWS + 1;      // LDS row stride: (k*LDR + r) % 32 distinct over k
@@ -130,10 +119,7 @@ __global__ __launch_bounds__(256, EMIT ? 3 : 4) void k_mid_fit_v5(float* __restr
   typedef FitPart<HID> PT;
 // (rows per pass of the reduction product: 32; 16 halves the panels -- 22.7 instead of 39 KiB of LDS per workgroup --
 // and measured slower, 877 / 1071 against 857 / 985 us: occupancy is not limited by the LDS here)
-#ifndef RC_V5_PLD
-#define RC_V5_PLD 33
-#endif
-  constexpr int WLD = 32, PLD = RC_V5_PLD, GA = 11;    // padded weight rows; panel row stride (rows per pass + 1); gW3 values in the A panel
+  constexpr int WLD = 32, PLD = 33, GA = 11;    // padded weight rows; panel row stride (rows per pass + 1); gW3 values in the A panel
   constexpr int PANEL = (2 * 32 * PLD > 528 ? 2 * 32 * PLD : 528);   // floats per wavefront: A panel | B panel (later: its record)
   __shared__ __attribute__((aligned(16))) float sW2[HID * WLD];        // W2[m][i]   (i >= HID: zeros)
   __shared__ __attribute__((aligned(16))) float sW2T[HID * WLD];       // W2[j][k] stored as [k][j]
@@ -378,14 +364,12 @@ __global__ __launch_bounds__(256, EMIT ? 3 : 4) void k_mid_fit_v5(float* __restr
 // History: the same data flow on three exact bf16 pieces (six products, 9 VALU per split pair; "v7") ran
 // 827 us against v5's 797 at BASELINE configs[3] -- the splits, plane traffic and dependent MFMA chains gave back what the
 // matrix core saved; with two f16 pieces it runs ~600 us against v5's ~715 (profiles/r03n_mid_ab.txt).
-#ifndef RC_V8_WAVES
-#define RC_V8_WAVES 3                    // wavefronts per SIMD the register allocation aims at
-#endif
+constexpr int kV8Waves = 3;              // wavefronts per SIMD the register allocation aims at
 #define RC_V8_S 1024.f                   // scale of W2 and of dz2
 #define RC_V8_US 0.0009765625f
 #define RC_V8_RANGE 65000.f              // a (scaled) operand beyond this would saturate: the agent is flagged and redone by k_mid_fit_v5
 template <int HID, bool EMIT>
-__global__ __launch_bounds__(256, RC_V8_WAVES) void k_mid_fit_v8(float* __restrict__ a1t, const float* __restrict__ theta,
+__global__ __launch_bounds__(256, kV8Waves) void k_mid_fit_v8(float* __restrict__ a1t, const float* __restrict__ theta,
                                                     const float* __restrict__ y, float* __restrict__ partials, int N,
                                                     int B, int in_dim, int ldp, int ldb, int nchunk, int cpw,
                                                     unsigned char* __restrict__ dzp, int dzp_rt, int dzp_kt,
@@ -574,10 +558,8 @@ __global__ __launch_bounds__(256, RC_V8_WAVES) void k_mid_fit_v8(float* __restri
       rc_f32x16 zz;
 #pragma unroll
       for (int q = 0; q < 16; ++q) zz[q] = 0.f;
-      RC_MX_BEGIN();
-      zz = v8_mfma4(loadA(0, 1), pa1, zz);
-      zz = v8_mfma4(loadA(0, 0), pa0, zz);
-      RC_MX_END();
+      zz = v8_mfma<kMidDropLL>(loadA(0, 1), pa1, zz);
+      zz = v8_mfma<kMidDropLL>(loadA(0, 0), pa0, zz);
       RC_SCHED_FENCE();
       // a2 = lrelu(z2 + b2) two units at a time (max(z, leak z): bit for bit the select form), v = a2 . W3 + b3
       rc_f2 a2p[LU / 2], w3p[LU / 2];
@@ -628,10 +610,8 @@ __global__ __launch_bounds__(256, RC_V8_WAVES) void k_mid_fit_v8(float* __restri
       rc_f32x16 dd;
 #pragma unroll
       for (int q = 0; q < 16; ++q) dd[q] = 0.f;
-      RC_MX_BEGIN();
-      dd = v8_mfma4(loadA(1, 1), pd1, dd);
-      dd = v8_mfma4(loadA(1, 0), pd0, dd);
-      RC_MX_END();
+      dd = v8_mfma<kMidDropLL>(loadA(1, 1), pd1, dd);
+      dd = v8_mfma<kMidDropLL>(loadA(1, 0), pd0, dd);
       RC_SCHED_FENCE();
       // dz1 = (dd * scale) * (a1 > 0 ? 1 : leak)   (EMIT: 2^8 dz1, what the packed operand carries)
       float dz1l[LU];
@@ -665,7 +645,7 @@ __global__ __launch_bounds__(256, RC_V8_WAVES) void k_mid_fit_v8(float* __restri
         rb.h.x = t0.x; rb.h.y = t0.y; rb.h.z = t1.x; rb.h.w = t1.y;
         t0 = rc_lds_read_tr16(pB + 1 * PLANE + o); t1 = rc_lds_read_tr16(pB + 1 * PLANE + o4);
         rb.l.x = t0.x; rb.l.y = t0.y; rb.l.z = t1.x; rb.l.w = t1.y;
-        g1 = v8_mfma4(ra, rb, g1);
+        g1 = v8_mfma<kMidDropLL>(ra, rb, g1);
         RC_SCHED_FENCE();                              // (keeps the second k-step's eight reads from being hoisted: registers)
       }
       if (EMIT) {
@@ -873,23 +853,9 @@ __global__ __launch_bounds__(256) void k_consensus_head(const float* __restrict_
 #define RC_K2MX_S3 1024.f
 #define RC_K2MX_ONE_H2 0x3C003C00u       // f16 (1.0, 1.0): the two bias slots of layer 2
 #define RC_K2MX_ONE_H3 0x54005400u       // f16 (64.0, 64.0): the heads' bias slots (phi arrives as 2^6 phi)
-#ifndef RC_K2MX_WAVES
-#define RC_K2MX_WAVES 3                  // wavefronts per SIMD the register allocation aims at (161 registers; 4 spills, 2 leaves 192 unused)
-#endif
-// The product of the two LOW pieces (<= 2^-22 of a term: a quarter of an fp32 rounding step of it) is left out, as in the packed-operand
-// GEMMs of the wide critic: three matrix-core passes per k-step instead of four (RC_K2MX_DROP_LL=0 restores it).
-#ifndef RC_K2MX_DROP_LL
-#define RC_K2MX_DROP_LL RC_V8_DROP_LL
-#endif
-__device__ __forceinline__ rc_f32x16 k2_mfma(const V8Pieces& a, const V8Pieces& b, rc_f32x16 c) {
-  if (!RC_K2MX_DROP_LL) c = rc_mfma_f16(a.l, b.l, c);
-  c = rc_mfma_f16(a.l, b.h, c);
-  c = rc_mfma_f16(a.h, b.l, c);
-  c = rc_mfma_f16(a.h, b.h, c);
-  return c;
-}
+constexpr int kK2mxWaves = 3;            // wavefronts per SIMD the register allocation aims at (161 registers; 4 spills, 2 leaves 192 unused)
 template <int D, int H>
-__global__ __launch_bounds__(256, RC_K2MX_WAVES) void k_consensus_head_mx(const float* __restrict__ a1t, const float* __restrict__ theta,
+__global__ __launch_bounds__(256, kK2mxWaves) void k_consensus_head_mx(const float* __restrict__ a1t, const float* __restrict__ theta,
                                                            const float* __restrict__ msg, const int* __restrict__ nbr,
                                                            const int* __restrict__ coop, float* __restrict__ partials,
                                                            float* __restrict__ agg_out, int N, int B, int in_dim, int ldp, int ldb,
@@ -1017,10 +983,8 @@ __global__ __launch_bounds__(256, RC_K2MX_WAVES) void k_consensus_head_mx(const 
         rc_f32x16 zz;
 #pragma unroll
         for (int q = 0; q < 16; ++q) zz[q] = 0.f;
-        RC_MX_BEGIN();
-        zz = k2_mfma(loadA(wfA, 0), pa0[blk], zz);
-        zz = k2_mfma(loadA(wfA, 1), pa1[blk], zz);                        // (the k-step with the bias last: it joins a finished sum)
-        RC_MX_END();
+        zz = v8_mfma<kMidDropLL>(loadA(wfA, 0), pa0[blk], zz);
+        zz = v8_mfma<kMidDropLL>(loadA(wfA, 1), pa1[blk], zz);             // (the k-step with the bias last: it joins a finished sum)
         float np = 0.f;
 #pragma unroll
         for (int u = 0; u < LU; ++u) {
@@ -1043,10 +1007,8 @@ __global__ __launch_bounds__(256, RC_K2MX_WAVES) void k_consensus_head_mx(const 
         rc_f32x16 ee;
 #pragma unroll
         for (int q = 0; q < 16; ++q) ee[q] = 0.f;
-        RC_MX_BEGIN();
-        ee = k2_mfma(loadA(hfA, 0), p0, ee);
-        ee = k2_mfma(loadA(hfA, 1), p1, ee);
-        RC_MX_END();
+        ee = v8_mfma<kMidDropLL>(loadA(hfA, 0), p0, ee);
+        ee = v8_mfma<kMidDropLL>(loadA(hfA, 1), p1, ee);
 #pragma unroll
         for (int q = 0; q < 16; ++q) est[blk][q] = ee[q];
       }
@@ -1245,8 +1207,8 @@ __global__ __launch_bounds__(256, 4) void k_mid_value_mx(const float* __restrict
       rc_f32x16 zz;
 #pragma unroll
       for (int q = 0; q < 16; ++q) zz[q] = 0.f;
-      zz = k2_mfma(loadA(0), pa0[blk], zz);
-      zz = k2_mfma(loadA(1), pa1[blk], zz);
+      zz = v8_mfma<kMidDropLL>(loadA(0), pa0[blk], zz);
+      zz = v8_mfma<kMidDropLL>(loadA(1), pa1[blk], zz);
       float acc = 0.f;
 #pragma unroll
       for (int u = 0; u < LU; ++u) {

@@ -575,6 +575,7 @@ constexpr size_t MX_CBYTES = (size_t)MX_CF16 * 2 + MX_PARAMS * 4;
 #define MX_S 1024.f
 #define MX_US 0.0009765625f
 #define MX_RANGE 65000.f
+constexpr bool kMxDropLL = false;                                // all four piece products per k-step (v8_mfma, rcmarl_lattice.h)
 
 __device__ __forceinline__ int mx_row_of_unit(int u) { return u < 16 ? 8 * ((u & 7) >> 2) + 4 * (u >> 3) + (u & 3) : 16 + 4 * ((u - 16) >> 1) + ((u - 16) & 1); }
 __device__ __forceinline__ int mx_slot_of_unit(int u) { return u < 16 ? u : 16 + 8 * ((u - 16) >> 1) + ((u - 16) & 1); }
@@ -782,8 +783,8 @@ __device__ __forceinline__ void mx_fit_net(const MbArgs& a, int net, unsigned ch
       rc_f32x16 zz;
 #pragma unroll
       for (int q = 0; q < 16; ++q) zz[q] = 0.f;
-      if (KS1 == 2) zz = v8_mfma4(loadA(0, 1), px1, zz);
-      zz = v8_mfma4(loadA(0, 0), px0, zz);
+      if (KS1 == 2) zz = v8_mfma<kMxDropLL>(loadA(0, 1), px1, zz);
+      zz = v8_mfma<kMxDropLL>(loadA(0, 0), px0, zz);
       float a1[LU];
 #pragma unroll
       for (int u = 0; u < LU; ++u) a1[u] = rc_lrelu(fmaf(zz[u], MX_US, prm[v8_unit(half, u)]));
@@ -801,8 +802,8 @@ __device__ __forceinline__ void mx_fit_net(const MbArgs& a, int net, unsigned ch
       *reinterpret_cast<unsigned*>(pA1 + MX_PA / 2 + wr2A) = pa1.l.x;
 #pragma unroll
       for (int q = 0; q < 16; ++q) zz[q] = 0.f;
-      zz = v8_mfma4(loadA(1, 1), pa1, zz);
-      zz = v8_mfma4(loadA(1, 0), pa0, zz);
+      zz = v8_mfma<kMxDropLL>(loadA(1, 1), pa1, zz);
+      zz = v8_mfma<kMxDropLL>(loadA(1, 0), pa0, zz);
       float a2[LU], vp = 0.f;
 #pragma unroll
       for (int u = 0; u < LU; ++u) a2[u] = rc_lrelu(fmaf(zz[u], MX_US, prm[HID + v8_unit(half, u)]));
@@ -849,13 +850,13 @@ __device__ __forceinline__ void mx_fit_net(const MbArgs& a, int net, unsigned ch
       rc_f32x16 dd;
 #pragma unroll
       for (int q = 0; q < 16; ++q) dd[q] = 0.f;
-      dd = v8_mfma4(loadA(2, 1), pd1, dd);
-      dd = v8_mfma4(loadA(2, 0), pd0, dd);
+      dd = v8_mfma<kMxDropLL>(loadA(2, 1), pd1, dd);
+      dd = v8_mfma<kMxDropLL>(loadA(2, 0), pd0, dd);
       if (COMPACT) {                                           // G1 now: its B planes are about to be overwritten by G2's
         RC_WAVE_SYNC();
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
-          g1 = v8_mfma4(readT(pA1, MX_PA / 2, trA + 16 * MX_PCA * ks, MX_PCA), readT(pB1, MX_PB / 2, trB + 16 * MX_PCB * ks, MX_PCB), g1);
+          g1 = v8_mfma<kMxDropLL>(readT(pA1, MX_PA / 2, trA + 16 * MX_PCA * ks, MX_PCA), readT(pB1, MX_PB / 2, trB + 16 * MX_PCB * ks, MX_PCB), g1);
       }
       float dz1[LU];                                           // 2^10 dz1
 #pragma unroll
@@ -898,7 +899,7 @@ __device__ __forceinline__ void mx_fit_net(const MbArgs& a, int net, unsigned ch
         RC_WAVE_SYNC();
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
-          g2 = v8_mfma4(readT(pA2, MX_PA / 2, trA + 16 * MX_PCA * ks, MX_PCA), readT(pB2, MX_PB / 2, trB + 16 * MX_PCB * ks, MX_PCB), g2);
+          g2 = v8_mfma<kMxDropLL>(readT(pA2, MX_PA / 2, trA + 16 * MX_PCA * ks, MX_PCA), readT(pB2, MX_PB / 2, trB + 16 * MX_PCB * ks, MX_PCB), g2);
       }
       if (last_tile) {
         // ---- SGD step: the owner of a gradient slot holds the parameter's fp32 master and refreshes its broadcast copies

@@ -84,16 +84,12 @@ __device__ __forceinline__ void rc_split3_pair(float w0, float w1, unsigned& h, 
 // operand, bit 1 = backward operand in this form; 0 = the exact three-piece bf16 form everywhere.
 #define RC_F16_W_SCALE 1024.f
 #define RC_F16_W_UNSCALE 0.0009765625f
-#ifndef RC_F16_DZ_SCALE                 // (A/B builds: -DRC_F16_DZ_SCALE=65536.f -DRC_F16_DZ_UNSCALE=1.52587890625e-05f in every source)
 #define RC_F16_DZ_SCALE 256.f
 #define RC_F16_DZ_UNSCALE 0.00390625f
-#endif
 // activations of a wide network as two f16 pieces (wide_kernels.hip, dense_pk.hip): full precision from |a| >= 2.0e-3, finite to 1015
 #define RC_F16_ACT_SCALE 64.f
 #define RC_F16_ACT_UNSCALE 0.015625f
-#ifndef RC_LAT_F16_DEFAULT
 #define RC_LAT_F16_DEFAULT 3
-#endif
 // (csrc/abi.hip) the operand form -- RCMARL_LAT_F16 read once, then rcmarl_lattice_set_f16_mode -- and the form each packed
 // buffer was last WRITTEN in: producers record it, consumers refuse a buffer written in the other form (RCMARL_ERR_ARG)
 int rc_lat_f16_mode();
@@ -151,7 +147,7 @@ typedef _Float16 rc_h2 __attribute__((ext_vector_type(2)));
 // f16) -- the plain form (convert h back, packed subtract, packed convert) is five, and hipcc folds any C++ spelling of the FMA
 // back into it.  Hence inline asm, which the compiler's hazard recognizer does not look into: a write to the HIGH half of a
 // register (v_fma_mixhi) must be one wait state away from a vector instruction that reads the register, and two from an MFMA
-// -- the s_nop closing each block (without it the fused prototypes read stale pieces: tools/prototypes/fused_fit.hip, round 4).
+// -- the s_nop closing each block (without it the fused prototypes of round 4 read stale pieces).
 #define RC_MIXLO(d, h, v) "v_fma_mixlo_f16 " d ", -" h ", 1.0, " v " op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
 #define RC_MIXHI(d, h, v) "v_fma_mixhi_f16 " d ", -" h ", 1.0, " v " op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
 __device__ __forceinline__ void rc_split2h_pair(float w0, float w1, unsigned& h, unsigned& l) {
@@ -268,12 +264,16 @@ __device__ __forceinline__ int v8_slot_unit(int k) {
 }
 
 struct V8Pieces { uint4 h, l; };
-// RC_V8_DROP_LL=1 (set by mid_kernels.hip for its kernels): the low x low pass left out.
-#ifndef RC_V8_DROP_LL
-#define RC_V8_DROP_LL 0
-#endif
-__device__ __forceinline__ rc_f32x16 v8_mfma4(const V8Pieces& a, const V8Pieces& b, rc_f32x16 c) {
-  if (!RC_V8_DROP_LL) c = rc_mfma_f16(a.l, b.l, c);
+// One k-step of a product of two-piece operands: c += (a.h + a.l) (b.h + b.l).  DROP_LL leaves out the product of the two LOW
+// pieces: it is at most 2^-22 of a term, a quarter of an fp32 rounding step of it, so three matrix-core passes instead of four.
+// Round 6 (visit l): in k_mid_fit_v8 this moves the gradient records by 0.7-1.5e-7 of their scale, LESS than the fp32 vector-ALU
+// form of the same kernel differs from the four-pass form through its summation order alone (2.2e-7;
+// profiles/r06l_mid_ab_drop_ll.txt), for 5 % of the kernel's time (434-440 -> 410-419 us).  The 20-unit kernels of mid_kernels.hip
+// take three passes, as the packed-operand GEMMs of the wide critic do; the adversaries' mini-batch chain (minibatch_fit.hip) keeps
+// all four.
+template <bool DROP_LL>
+__device__ __forceinline__ rc_f32x16 v8_mfma(const V8Pieces& a, const V8Pieces& b, rc_f32x16 c) {
+  if constexpr (!DROP_LL) c = rc_mfma_f16(a.l, b.l, c);
   c = rc_mfma_f16(a.l, b.h, c);
   c = rc_mfma_f16(a.h, b.l, c);
   c = rc_mfma_f16(a.h, b.h, c);

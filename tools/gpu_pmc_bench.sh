@@ -18,7 +18,7 @@ names = {"k_lat_forward<true, true, true>": "layer1_forward_lattice_pk", "k_lat_
          "k_consensus_head<": "consensus_head", "k_consensus_head_mx<": "consensus_head", "k_mid_value_mx<": "mid_value",
          "k_lat_forward<true, true, true>": "layer1_forward_lattice_pk", "k_pk_forward2": "pk_forward2", "k_pk_backward_data": "pk_backward_data",
          "k_pk_backward_w2": "pk_backward_w2", "k_pk_pack_w2": "pk_pack_w2", "k_mid_value": "mid_value", "k_lattice_encode": "lattice_encode",
-         "fast::k_fwd": "layer1_forward", "fast::k_bwd<1, (anonymous namespace)::fast::ApplySgd>": "layer1_backward_sgd",
+         "fast::k_fwd": "layer1_forward", "fast::k_bwd<(anonymous namespace)::fast::ApplySgd>": "layer1_backward_sgd",
          "k_mid_fit_v3<20, false": "mid_fit", "k_rollout_step_ep": "rollout_step_episodes"}
 tot = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.defaultdict(lambda: collections.Counter())
 for f in glob.glob('$R/gpurun_out/pmcb/${W}_*counter_collection.csv'):
