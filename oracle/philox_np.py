@@ -72,6 +72,23 @@ def sample_actions(probs, seed, episode, step, mu=0.1):
     return np.where(u2 < thr, a_pol, a_rand).astype(np.int64)
 
 
+def action_margins(probs, seed, episode, step):
+    """How far the policy draw of `sample_actions` is from changing its answer: min_k |u1 - cumsum_fp32(p)[k]| over the A-1
+    boundaries the draw is compared with, per agent (float64).  probs: [..., N, A]; episode: scalar or an array that broadcasts
+    against the leading axes of probs[..., 0] (e.g. [E, 1] for probs [E, N, A])."""
+    probs = np.asarray(probs, dtype=np.float32)
+    N, A = probs.shape[-2:]
+    k0, k1 = seed_key(seed)
+    _, r1, _, _ = philox4x32(np.arange(N), step, episode, 0, k0, k1)
+    u1 = np.broadcast_to(u01(r1), probs.shape[:-1]).astype(np.float64)
+    c = np.zeros(probs.shape[:-1], np.float32)
+    margin = np.full(probs.shape[:-1], np.inf)
+    for k in range(A - 1):
+        c = (c + probs[..., k]).astype(np.float32)
+        margin = np.minimum(margin, np.abs(u1 - c.astype(np.float64)))
+    return margin
+
+
 def reset_positions(n_agents, nrow, ncol, seed, episode):
     """Device-mode replacement of np.random.randint([0,0],[nrow,ncol],(N,2))
     (environments/grid_world.py:40)."""

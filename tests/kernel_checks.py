@@ -519,7 +519,10 @@ def check_reward_helpers(bk, S, N, B):
     a, b, c = (rng.normal(size=1000).astype(np.float32) for _ in range(3))
     d_o, d_a, d_b, d_c = bk.dev(np.zeros(1000, np.float32)), bk.dev(a), bk.dev(b), bk.dev(c)
     L.rcmarl_td_error(bk.ptr(d_a), bk.ptr(d_b), bk.ptr(d_c), 0.9, bk.ptr(d_o), 1000, bk.stream)
-    np.testing.assert_allclose(bk.host(d_o), a + np.float32(0.9) * b - c, rtol=1e-6, atol=1e-7)
+    # r + gamma*nV - V (agents/resilient_CAC_agents.py:98) with every operation rounded to fp32, in that order (the library is built
+    # without fp contraction): bits
+    want = ((a + (np.float32(0.9) * b).astype(np.float32)).astype(np.float32) - c).astype(np.float32)
+    np.testing.assert_array_equal(bk.host(d_o).view(np.uint32), want.view(np.uint32))
 
 
 # ------------------------------------------------------------------------------------------
@@ -1375,3 +1378,337 @@ def check_consensus_on_shipped_weights(bk, golden):
 
 
 # ------------------------------------------------------------------------------------------
+SENT = -7           # NaN-free sentinel of the "nothing else written" checks: untouched memory compares EQUAL to it
+KNIFE_EDGE = 1.2e-5      # a policy draw this close to a cdf boundary may fall either way: 4 cdf terms x the 3e-6 bar on a probability
+KNIFE_EDGE_CAP = 1e-3    # share of a case's draws that may be knife edges (expected: 8 boundaries' sides x 1.2e-5 ~ 1e-4)
+
+
+def check_rollout_episodes(bk, S, N, nrow, ncol, E, ep_len, episode0, row0, pos_in=False):
+    """The episode-parallel rollout (rcmarl_env_reset_episodes, rcmarl_value_rows_episodes, rcmarl_rollout_step_episodes: one lane =
+    one episode, episode-minor state) against one oracle environment per (seed, episode): start positions (Philox, or pos_in),
+    scaled states, start-state values, every replay row, positions and float64 returns EXACTLY, with every buffer pre-filled with a
+    sentinel so that the padding lanes E..EP, the est entries past E and the replay rows outside [row0, row0 + E*ep_len) are shown
+    untouched after every launch.  The oracle is stepped with the KERNEL's actions; an action may differ from the oracle's draw only
+    where u1 is within KNIFE_EDGE of a cdf boundary (printed), and at most KNIFE_EDGE_CAP of the draws may be that close.  The last
+    episode of seed 0 is replayed with the sequential kernels (rcmarl_env_reset + rcmarl_rollout_step) and must leave the same rows,
+    positions and returns (skipped, with a note, if that episode holds a knife-edge draw).  Bad arguments are refused before anything
+    is written.  -> dict(draws, knife_edges, knife_flips, sequential_compared)"""
+    import pytest
+    from oracle import philox_np as PX
+    from rcmarl_amd import capi
+    rng = np.random.default_rng(S * 7 + N + 13 * E)
+    A = 5
+    in_a = 2 * N
+    Pa, _ = geom(in_a, A)
+    Pc, _ = geom(in_a, 1)
+    ldpa, ldpc = pad64(Pa), pad64(Pc)
+    actors = random_params(rng, S, N, in_a, A, bias_scale=0.3)
+    critics = random_params(rng, S, N, in_a, 1)
+    th_a, th_c = pack_rows(actors, ldpa), pack_rows(critics, ldpc)
+    goal = rng.integers(0, min(5, nrow), size=(S, N, 2)).astype(np.int32)
+    start = np.stack([rng.integers(0, nrow, size=(S, N)), rng.integers(0, ncol, size=(S, N))], axis=2).astype(np.int32) if pos_in else None
+    seeds = np.array([1000 + 17 * s for s in range(S)], dtype=np.uint64)
+    mean = np.array([np.mean(np.arange(nrow)), np.mean(np.arange(ncol))])
+    std = np.array([np.std(np.arange(nrow)), np.std(np.arange(ncol))])
+    scale = np.concatenate([mean, std])
+    EP = pad64(E)
+    cap = row0 + E * ep_len + 5
+    gamma, mu = 0.9, 0.1
+    widths = (("s", 2), ("ns", 2), ("sa", 3), ("a", 1), ("r", 1))
+    L = bk.lib
+    d_tha, d_thc, d_goal, d_seeds, d_scale = bk.dev(th_a), bk.dev(th_c), bk.dev(goal), bk.dev(seeds), bk.dev(scale)
+    d_start = bk.dev(start) if pos_in else None
+    # what every buffer is expected to hold, kept on the host beside it: compared WHOLE after every launch
+    want_rp = {k: np.full((S, cap, w * N), SENT, np.float32) for k, w in widths}
+    want_est = np.full((E + 2, S, N), SENT, np.float32)
+    want_pos = [np.full((S, N, 2, EP), SENT, np.int32) for _ in range(2)]
+    want_xs = [np.full((S, 2 * N, EP), SENT, np.float32) for _ in range(2)]
+    want_ret = np.full((S, N, EP), SENT, np.float64)
+    rp = {k: bk.dev(v) for k, v in want_rp.items()}
+    d_est, d_ret = bk.dev(want_est), bk.dev(want_ret)
+    d_pos, d_xs = [bk.dev(v) for v in want_pos], [bk.dev(v) for v in want_xs]
+
+    def reset(E_, EP_):
+        return L.rcmarl_env_reset_episodes(bk.ptr(d_start) if pos_in else None, bk.ptr(d_seeds), nrow, ncol, bk.ptr(d_scale), episode0,
+                                           bk.ptr(d_pos[0]), bk.ptr(d_xs[0]), bk.ptr(d_ret), S, N, E_, EP_, bk.stream)
+
+    def values(E_, EP_):
+        return L.rcmarl_value_rows_episodes(bk.ptr(d_xs[0]), bk.ptr(d_thc), bk.ptr(d_est), S, N, E_, EP_, HID, ldpc, bk.stream)
+
+    def step(cur, j, gpow, E_=E, EP_=EP, cap_=cap):
+        return L.rcmarl_rollout_step_episodes(bk.ptr(d_xs[cur]), bk.ptr(d_pos[cur]), bk.ptr(d_goal), bk.ptr(d_tha), bk.ptr(d_seeds), nrow,
+                                              ncol, bk.ptr(d_scale), bk.ptr(rp["s"]), bk.ptr(rp["ns"]), bk.ptr(rp["sa"]), bk.ptr(rp["a"]),
+                                              bk.ptr(rp["r"]), cap_, row0, ep_len, bk.ptr(d_pos[1 - cur]), bk.ptr(d_xs[1 - cur]),
+                                              bk.ptr(d_ret), gpow, episode0, j, mu, S, N, E_, EP_, HID, A, ldpa, bk.stream)
+
+    def assert_state(what):
+        for k, _ in widths:
+            np.testing.assert_array_equal(bk.host(rp[k]), want_rp[k], err_msg="%s: replay tensor %s" % (what, k))
+        np.testing.assert_array_equal(bk.host(d_est), want_est, err_msg="%s: est" % what)
+        np.testing.assert_array_equal(bk.host(d_ret), want_ret, err_msg="%s: retT" % what)
+        for c in range(2):
+            np.testing.assert_array_equal(bk.host(d_pos[c]), want_pos[c], err_msg="%s: posT[%d]" % (what, c))
+            np.testing.assert_array_equal(bk.host(d_xs[c]), want_xs[c], err_msg="%s: xsT[%d]" % (what, c))
+
+    # ---- refused argument sets: RCMARL_ERR_ARG, nothing written ---------------------------------------------------------
+    bad = [lambda: reset(E, EP - 64), lambda: reset(E, EP + 8), lambda: values(E, EP - 64), lambda: values(E, EP + 8),
+           lambda: step(0, 0, 1.0, EP_=EP - 64), lambda: step(0, 0, 1.0, EP_=EP + 8), lambda: step(0, ep_len, 1.0),
+           lambda: step(0, 0, 1.0, cap_=row0 + E * ep_len - 1)]
+    for call in bad:
+        with pytest.raises(capi.RcmarlError, match="RCMARL_ERR_ARG"):
+            call()
+    assert_state("after the refused calls")
+
+    # ---- reset ------------------------------------------------------------------------------------------------------
+    reset(E, EP)
+    envs = []
+    for s in range(S):
+        row = []
+        for e in range(E):
+            env = O.GridWorldOracle(nrow, ncol, N, goal[s], start[s] if pos_in else None, not pos_in, True, rng_mode="device", seed=int(seeds[s]))
+            env.reset(episode=episode0 + e)
+            if pos_in:
+                np.testing.assert_array_equal(env.state, start[s])
+            else:
+                np.testing.assert_array_equal(env.state, PX.reset_positions(N, nrow, ncol, int(seeds[s]), episode0 + e))
+            row.append(env)
+        envs.append(row)
+
+    def scaled(pos_t):
+        """int positions [S][N][2][lanes] -> the state vector [S][2N][lanes]: float32 of the float64 (pos - mean) / std"""
+        x = (pos_t.astype(np.float64) - mean[None, None, :, None]) / std[None, None, :, None]
+        return x.astype(np.float32).reshape(pos_t.shape[0], 2 * N, pos_t.shape[3])
+
+    def states():
+        """the environments' positions, episode-minor [S][N][2][E]"""
+        return np.stack([np.stack([env.state for env in row], axis=2) for row in envs]).astype(np.int32)
+
+    want_pos[0][...] = 0                                 # the padding lanes: cell 0, its scaled value, return 0 (as documented)
+    want_pos[0][:, :, :, :E] = states()
+    want_xs[0] = scaled(want_pos[0])
+    want_ret[...] = 0.0
+    assert_state("after the reset")
+    for s in range(S):                                   # (the oracle's own get_data() gives the same float32 vector)
+        for e in (0, E - 1):
+            np.testing.assert_array_equal(want_xs[0][s, :, e], envs[s][e].get_data()[0].astype(np.float32).ravel())
+
+    # ---- start-state values -----------------------------------------------------------------------------------------
+    values(E, EP)
+    est = bk.host(d_est)
+    for s in range(S):
+        X = np.ascontiguousarray(want_xs[0][s, :, :E].T)                       # [E][2N]
+        for i in range(N):
+            want = M.forward(critics[s][i], X)[:, 0]
+            err = np.abs(est[:E, s, i] - want)
+            assert np.all(err <= 3e-6 * np.maximum(1.0, np.abs(want))), ("start value", s, i, float(err.max()))
+    want_est[:E] = est[:E]
+    assert_state("after the start-state values")
+
+    # ---- steps ------------------------------------------------------------------------------------------------------
+    ret64 = np.zeros((S, N, E))
+    n_draws = n_knife = n_flip_knife = 0
+    knife_in_last_episode = False
+    cur = 0
+    for j in range(ep_len):
+        gpow = float(gamma ** j)
+        step(cur, j, gpow)
+        rows = row0 + np.arange(E) * ep_len + j
+        act_k = bk.host(rp["a"])[:, rows, :]                                    # [S][E][N], the kernel's actions
+        assert np.all((act_k == np.round(act_k)) & (act_k >= 0) & (act_k < A)), "step %d: actions outside 0..%d" % (j, A - 1)
+        act_k = act_k.astype(np.int64)
+        for s in range(S):
+            X = np.ascontiguousarray(want_xs[cur][s, :, :E].T)                  # [E][2N]: every episode's state, one forward per agent
+            op = np.stack([M.softmax(M.forward(actors[s][i], X)) for i in range(N)], axis=1)            # [E][N][A] fp32
+            act_o = np.stack([PX.sample_actions(op[e], int(seeds[s]), episode0 + e, j, mu) for e in range(E)])
+            knife = PX.action_margins(op, int(seeds[s]), episode0 + np.arange(E)[:, None], j) <= KNIFE_EDGE
+            flip = act_k[s] != act_o
+            n_draws += flip.size
+            n_knife += int(knife.sum())
+            n_flip_knife += int((flip & knife).sum())
+            if s == 0 and knife[E - 1].any():
+                knife_in_last_episode = True
+            for e, i in zip(*np.nonzero(flip & knife)):
+                print("[rollout episodes] knife-edge draw fell the other way: seed %d episode %d step %d agent %d: kernel %d, oracle %d"
+                      % (s, episode0 + e, j, i, act_k[s, e, i], act_o[e, i]))
+            assert not (flip & ~knife).any(), ("actions differ from the oracle's Philox draw away from any cdf boundary: step %d, seed %d, "
+                                               "(episode, agent) %s" % (j, s, list(zip(*np.nonzero(flip & ~knife)))[:8]))
+            for e in range(E):
+                env = envs[s][e]
+                st = env.get_data()[0].astype(np.float32)
+                env.step(act_k[s, e].astype(np.float64))
+                nst, rew = env.get_data()
+                a32 = act_k[s, e].astype(np.float32)
+                ret64[s, :, e] += rew * (gamma ** j)
+                want_rp["s"][s, rows[e]] = st.ravel()
+                want_rp["ns"][s, rows[e]] = nst.astype(np.float32).ravel()
+                want_rp["sa"][s, rows[e]] = np.concatenate([st, a32[:, None]], axis=1).ravel()
+                want_rp["a"][s, rows[e]] = a32
+                want_rp["r"][s, rows[e]] = rew.astype(np.float32)
+        nxt = 1 - cur
+        want_pos[nxt][:, :, :, :E] = states()                                   # lanes E..EP keep what they held (the sentinel, or an
+        want_xs[nxt][:, :, :E] = scaled(want_pos[nxt][:, :, :, :E])             # earlier step's output of lanes < E only)
+        want_ret[:, :, :E] = ret64
+        assert_state("after step %d" % j)                                       # incl. the step's INPUT copy of posT / xsT: unchanged
+        cur = nxt
+    share = n_knife / max(1, n_draws)
+    print("[rollout episodes] S=%d N=%d %dx%d E=%d ep_len=%d episode0=%d row0=%d%s: %d draws, %d knife edges (%.4f %%), %d of them fell "
+          "the other way" % (S, N, nrow, ncol, E, ep_len, episode0, row0, " pos_in" if pos_in else "", n_draws, n_knife, 100.0 * share,
+                             n_flip_knife))
+    assert share <= KNIFE_EDGE_CAP, "knife-edge share %.3e of this case's draws: pick another seed for the case" % share
+
+    # ---- the sequential kernels on the last episode of seed 0 -------------------------------------------------------------------
+    if knife_in_last_episode:
+        print("[rollout episodes] episode %d of seed 0 holds a knife-edge draw: sequential-vs-parallel comparison skipped" % (episode0 + E - 1))
+        return dict(draws=n_draws, knife_edges=n_knife, knife_flips=n_flip_knife, sequential_compared=False)
+    q_rp = {k: bk.dev(np.full((1, ep_len, w * N), SENT, np.float32)) for k, w in widths}
+    q_pos = [bk.dev(np.full((1, N, 2), SENT, np.int32)) for _ in range(2)]
+    q_xs = [bk.dev(np.full((1, 2 * N), SENT, np.float32)) for _ in range(2)]
+    q_ret = bk.dev(np.full((1, N), SENT, np.float64))
+    ep_last = episode0 + E - 1
+    L.rcmarl_env_reset(bk.ptr(d_start) if pos_in else None, bk.ptr(d_seeds), nrow, ncol, bk.ptr(d_scale), ep_last, bk.ptr(q_pos[0]),
+                       bk.ptr(q_xs[0]), bk.ptr(q_ret), 1, N, bk.stream)
+    qc = 0
+    for j in range(ep_len):
+        L.rcmarl_rollout_step(bk.ptr(q_xs[qc]), bk.ptr(q_pos[qc]), bk.ptr(d_goal), bk.ptr(d_tha), bk.ptr(d_seeds), nrow, ncol,
+                              bk.ptr(d_scale), bk.ptr(q_rp["s"]), bk.ptr(q_rp["ns"]), bk.ptr(q_rp["sa"]), bk.ptr(q_rp["a"]),
+                              bk.ptr(q_rp["r"]), ep_len, j, bk.ptr(q_pos[1 - qc]), bk.ptr(q_xs[1 - qc]), bk.ptr(q_ret), float(gamma ** j),
+                              ep_last, j, mu, 1, N, HID, A, ldpa, None, bk.stream)
+        qc = 1 - qc
+    first = row0 + (E - 1) * ep_len
+    for k, _ in widths:
+        np.testing.assert_array_equal(bk.host(q_rp[k])[0], bk.host(rp[k])[0, first:first + ep_len], err_msg="sequential vs episode-parallel: " + k)
+    np.testing.assert_array_equal(bk.host(q_pos[qc])[0], bk.host(d_pos[cur])[0, :, :, E - 1])
+    np.testing.assert_array_equal(bk.host(q_xs[qc])[0], bk.host(d_xs[cur])[0, :, E - 1])
+    np.testing.assert_array_equal(bk.host(q_ret)[0], bk.host(d_ret)[0, :, E - 1])
+    return dict(draws=n_draws, knife_edges=n_knife, knife_flips=n_flip_knife, sequential_compared=True)
+
+
+# ------------------------------------------------------------------------------------------
+def check_row_helpers(bk, S, N, B, ep, width):
+    """The TD-target shortcut's two helpers (engine._value_next_cached*), every `ep`-th row starting at ep - 1:
+    rcmarl_gather_rows on a replay tensor addressed as the engine does (base pointer row0 rows in, seed stride = the whole capacity)
+    == the NumPy slice, nothing written behind dst; rcmarl_scatter_values, both forms == v, resp. float32(r + float32(gamma * v)) to
+    the BIT, every other entry of out untouched, a last row beyond ldb refused; and the identity the shortcut rests on: the TD target
+    rcmarl_mid_value(..., r_applied, gamma) leaves at those rows equals the two-call route -- rcmarl_mid_value(..., NULL) on the
+    gathered columns, then rcmarl_scatter_values.  With RCMARL_MIDVALUE_MX=0 both routes run the same fp32 lane code on a row: equal
+    bits.  With the matrix-core form (the default) a row's value may depend on its position in the 16-row tile, so there the two
+    routes are only held to the existing 3e-6 bar of check_mid_value."""
+    import pytest
+    from rcmarl_amd import capi
+    rng = np.random.default_rng(S * 11 + N * 5 + B + ep + width)
+    L = bk.lib
+    n_rows, first = B // ep, ep - 1
+    assert n_rows >= 1
+    # ---- gather ----
+    row0 = 3
+    cap = row0 + B + 4
+    src = rng.normal(size=(S, cap, width)).astype(np.float32)
+    dst0 = np.full(S * n_rows * width + 9, SENT, np.float32)
+    d_src, d_dst = bk.dev(src), bk.dev(dst0)
+    L.rcmarl_gather_rows(_ptr_add(bk.ptr(d_src), 4 * row0 * width), cap * width, first, ep, n_rows, width, bk.ptr(d_dst), S, bk.stream)
+    dst = bk.host(d_dst)
+    np.testing.assert_array_equal(dst[:S * n_rows * width].reshape(S, n_rows, width), src[:, row0 + first:row0 + B:ep][:, :n_rows])
+    np.testing.assert_array_equal(dst[S * n_rows * width:], dst0[S * n_rows * width:])
+    np.testing.assert_array_equal(bk.host(d_src), src)
+    # ---- scatter ----
+    ldb = pad64(B)
+    gamma = 0.9
+    v = rng.normal(size=(S, N, ldb)).astype(np.float32)
+    r_applied = rng.normal(size=(S, N, ldb)).astype(np.float32)
+    out0 = rng.normal(size=(S, N, ldb)).astype(np.float32)
+    d_v, d_r = bk.dev(v), bk.dev(r_applied)
+    cols = first + ep * np.arange(n_rows)
+    for with_r in (False, True):
+        d_out = bk.dev(out0)
+        L.rcmarl_scatter_values(bk.ptr(d_v), bk.ptr(d_r) if with_r else None, gamma, bk.ptr(d_out), first, ep, n_rows, S, N, ldb, bk.stream)
+        want = out0.copy()
+        if with_r:
+            gv = (np.float32(gamma) * v[:, :, :n_rows]).astype(np.float32)          # multiply, round, add, round
+            want[:, :, cols] = (r_applied[:, :, cols] + gv).astype(np.float32)
+        else:
+            want[:, :, cols] = v[:, :, :n_rows]
+        np.testing.assert_array_equal(bk.host(d_out).view(np.uint32), want.view(np.uint32), err_msg="scatter_values, r_applied %s" % with_r)
+    d_out = bk.dev(out0)
+    with pytest.raises(capi.RcmarlError, match="RCMARL_ERR_ARG"):                 # the last row would be column ldb
+        L.rcmarl_scatter_values(bk.ptr(d_v), bk.ptr(d_r), gamma, bk.ptr(d_out), ldb - (n_rows - 1) * ep, ep, n_rows, S, N, ldb, bk.stream)
+    np.testing.assert_array_equal(bk.host(d_out), out0)
+    # ---- the TD target through the shortcut == the TD target of the straight path ----
+    in_dim = 2 * N
+    P, _ = geom(in_dim, 1)
+    ldp = pad64(P)
+    theta = np.zeros((S, N, ldp), np.float32)
+    theta[:, :, :P] = (0.3 * rng.normal(size=(S, N, P))).astype(np.float32)
+    a1 = rng.normal(size=(S, N * HID, ldb)).astype(np.float32)
+    a1g = np.zeros_like(a1)
+    a1g[:, :, :n_rows] = a1[:, :, cols]
+    d_th, d_a, d_ag = bk.dev(theta), bk.dev(a1), bk.dev(a1g)
+    d_y, d_vg = bk.dev(np.full((S, N, ldb), SENT, np.float32)), bk.dev(np.full((S, N, ldb), SENT, np.float32))
+    d_out = bk.dev(out0)
+    L.rcmarl_mid_value(bk.ptr(d_a), bk.ptr(d_th), bk.ptr(d_r), gamma, bk.ptr(d_y), S, N, B, in_dim, HID, ldp, ldb, bk.stream)
+    L.rcmarl_mid_value(bk.ptr(d_ag), bk.ptr(d_th), None, gamma, bk.ptr(d_vg), S, N, n_rows, in_dim, HID, ldp, ldb, bk.stream)
+    L.rcmarl_scatter_values(bk.ptr(d_vg), bk.ptr(d_r), gamma, bk.ptr(d_out), first, ep, n_rows, S, N, ldb, bk.stream)
+    straight, two_call = bk.host(d_y)[:, :, cols], bk.host(d_out)[:, :, cols]
+    assert np.all(straight != np.float32(SENT)) and np.all(bk.host(d_vg)[:, :, n_rows:] == np.float32(SENT))
+    if os.environ.get("RCMARL_MIDVALUE_MX", "1") == "0" or bk.lib.rcmarl_lattice_f16_mode() == 0:
+        np.testing.assert_array_equal(two_call.view(np.uint32), straight.view(np.uint32), err_msg="TD target: shortcut vs straight path, fp32 lane code")
+    else:
+        rel_close(two_call, straight, 3e-6, "TD target: shortcut vs straight path, matrix-core form")
+
+
+COPY3D_DEFAULT = dict(batches=5, rows=3, cols=8, ld_src=12, ld_dst=12, pad_src=0, pad_dst=0, src_off=0, dst_off=0, mask="mixed", refused=False)
+COPY3D_CASES = {
+    # rcmarl_copy3d with more than 65535 batches (AdversaryPath publishes message rows with batches = seeds): the grid's z extent is
+    # capped and the kernel strides over the rest; masked rows stay untouched.
+    "more_batches_than_a_grid_dimension": dict(batches=70001),
+    # the 4-byte form k_copy3d<1>: a column block of the sharded instance that starts or ends at an odd offset
+    "odd_cols": dict(cols=7),
+    "odd_ld_src": dict(ld_src=13),
+    "odd_ld_dst": dict(ld_dst=15),
+    "odd_batch_strides": dict(pad_src=1, pad_dst=3),
+    "src_one_float_in": dict(src_off=1),
+    "dst_one_float_in": dict(dst_off=1),
+    "scalar_form_several_column_blocks": dict(cols=1027, ld_src=1030, ld_dst=1027, rows=2, batches=2),
+    # the 16-byte form k_copy3d<4>
+    "mask_null": dict(mask=None),
+    "mask_all_zero": dict(mask="zeros"),
+    "vector_form_several_column_blocks": dict(cols=2052, ld_src=2056, ld_dst=2060, rows=2, batches=2),        # blockIdx.x = 0..2, last ragged
+    # the early return and the refused shapes
+    "no_batches": dict(batches=0),
+    "no_rows": dict(rows=0, mask=None),
+    "ld_src_below_cols": dict(ld_src=4, refused=True),
+    "ld_dst_below_cols": dict(ld_dst=7, refused=True),
+}
+COPY3D_SMALL = [k for k in COPY3D_CASES if k != "more_batches_than_a_grid_dimension"]
+
+
+def check_copy3d(bk, case):
+    """rcmarl_copy3d (the pack pass of the sharded all-to-all, the adversaries' message rows): dst[b][r][:cols] = src[b][r][:cols] for
+    the rows the mask keeps == the NumPy box copy, and every float of dst outside the box keeps its previous contents (dst is random, so
+    a stray write shows).  `case` names an entry of COPY3D_CASES."""
+    import pytest
+    from rcmarl_amd import capi
+    c = dict(COPY3D_DEFAULT, **COPY3D_CASES[case])
+    rng = np.random.default_rng(9)
+    batches, rows, cols, ld_src, ld_dst = c["batches"], c["rows"], c["cols"], c["ld_src"], c["ld_dst"]
+    src_batch = max(rows, 1) * max(ld_src, cols) + c["pad_src"]
+    dst_batch = max(rows, 1) * max(ld_dst, cols) + c["pad_dst"]
+    src = rng.normal(size=c["src_off"] + max(batches, 1) * src_batch + 8).astype(np.float32)
+    dst0 = rng.normal(size=c["dst_off"] + max(batches, 1) * dst_batch + 8).astype(np.float32)
+    mask = {"mixed": np.array([1, 0, 1] * rows, np.int32)[:rows], "zeros": np.zeros(rows, np.int32), None: None}[c["mask"]]
+    d_src, d_dst = bk.dev(src), bk.dev(dst0)
+    d_mask = None if mask is None else bk.dev(mask)
+
+    def call():
+        return bk.lib.rcmarl_copy3d(_ptr_add(bk.ptr(d_src), 4 * c["src_off"]), src_batch, ld_src, _ptr_add(bk.ptr(d_dst), 4 * c["dst_off"]),
+                                    dst_batch, ld_dst, batches, rows, cols, None if mask is None else bk.ptr(d_mask), bk.stream)
+    want = dst0.copy()
+    if c["refused"]:
+        with pytest.raises(capi.RcmarlError, match="RCMARL_ERR_ARG"):
+            call()
+    else:
+        assert call() in (0, None)
+        keep = np.arange(rows) if mask is None else np.nonzero(mask)[0]
+        b, r, k = np.arange(batches)[:, None, None], keep[None, :, None], np.arange(cols)[None, None, :]
+        want[c["dst_off"] + b * dst_batch + r * ld_dst + k] = src[c["src_off"] + b * src_batch + r * ld_src + k]
+    np.testing.assert_array_equal(bk.host(d_dst), want)
+    np.testing.assert_array_equal(bk.host(d_src), src)

@@ -14,6 +14,17 @@ def test_engine_coop_matches_oracle(rng_mode):
     EC.compare(eng, logs, o_logs, o_w)
 
 
+def test_engine_blocks_of_more_than_64_episodes():
+    """n_ep_fixed = 70: the episode-parallel rollout runs two 64-lane blocks per (seed, agent) (EP = 128).  Blocks of 70, 70 and 5
+    episodes; the second block's 280 rows exceed buffer_size, so the oldest rows are dropped before the second update; the ragged last
+    block has no update after it (training/train_agents.py:86), only its returns and start-state estimates are logged.  The engine
+    carries the LAST episode's end positions over from lane n_eps - 1."""
+    args = EC.make_args(["Cooperative"] * 5, H=1, n_episodes=145, max_ep_len=2, n_ep_fixed=70, n_epochs=1, buffer_size=200, seed=81)
+    eng, logs, o_logs, o_w = EC.run_pair(args, 5, 5, "device", "cpu", emu_lib(), seeds=(81,))
+    assert eng.EP == 128 and eng.adam_t == 2
+    EC.compare(eng, logs, o_logs, o_w)
+
+
 def test_engine_common_reward_H0():
     args = EC.make_args(["Cooperative"] * 5, H=0, n_episodes=4, max_ep_len=3, n_ep_fixed=2, n_epochs=1, buffer_size=9, seed=5,
                         common_reward=True)

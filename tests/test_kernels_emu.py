@@ -154,6 +154,27 @@ def test_rollout(bk, S, N, nrow, ncol, mode):
     KC.check_rollout(bk, S, N, nrow, ncol, steps=5, mode=mode)
 
 
+@pytest.mark.parametrize("case", [(2, 5, 5, 5, 3, 4, 0, 0), (1, 6, 7, 9, 64, 2, 128, 7),
+                                  (2, 5, 5, 5, 70, 3, 50, 11),                 # two blocks of 64 lanes, the second ragged
+                                  (1, 7, 5, 5, 130, 2, 1000, 0, True)])        # three blocks, given start positions
+def test_rollout_episodes(bk, case):
+    """the episode-parallel rollout kernels the engine runs in rng_mode="device" (one lane = one episode), directly against the oracle"""
+    stats = KC.check_rollout_episodes(bk, *case)
+    assert stats["sequential_compared"]          # (no knife-edge draw in the replayed episode of any of these cases)
+
+
+@pytest.mark.parametrize("mx", ["1", "0"])       # the identity of the two TD-target routes: within 3e-6 | bit for bit
+@pytest.mark.parametrize("S,N,B,ep,width", [(2, 5, 60, 3, 10), (1, 3, 300, 20, 513), (1, 2, 8, 2, 1)])
+def test_row_helpers(bk, S, N, B, ep, width, mx, monkeypatch):
+    monkeypatch.setenv("RCMARL_MIDVALUE_MX", mx)
+    KC.check_row_helpers(bk, S, N, B, ep, width)
+
+
+@pytest.mark.parametrize("case", KC.COPY3D_SMALL)
+def test_copy3d(bk, case):
+    KC.check_copy3d(bk, case)
+
+
 @pytest.mark.parametrize("S,N,B,in_dim,advs,bs,shuffle", [(2, 5, 100, 10, [4], 32, True), (1, 5, 70, 15, [1, 3], 32, True),
                                                           (1, 2, 40, 140, [0], 32, False), (1, 6, 90, 18, [2, 5], 40, True),
                                                           (3, 5, 50, 20, [0], 7, True)])      # multi-tile batches, ragged tails

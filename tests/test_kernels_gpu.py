@@ -163,6 +163,25 @@ def test_rollout(bk, S, N, nrow, ncol, mode):
     KC.check_rollout(bk, S, N, nrow, ncol, steps=20, mode=mode)
 
 
+@pytest.mark.parametrize("case", [(2, 5, 5, 5, 3, 4, 0, 0), (1, 6, 7, 9, 64, 2, 128, 7),
+                                  (2, 5, 5, 5, 70, 3, 50, 11),                 # two blocks of 64 lanes, the second ragged
+                                  (1, 7, 5, 5, 130, 2, 1000, 0, True),         # three blocks, given start positions
+                                  (1, 256, 32, 32, 50, 3, 150, 2000),          # the benchmark shard's shape
+                                  (300, 5, 5, 5, 50, 2, 0, 0),                 # many seeds
+                                  (1, 64, 16, 16, 200, 2, 0, 40)])             # four blocks
+def test_rollout_episodes(bk, case):
+    """the episode-parallel rollout kernels the engine runs in rng_mode="device" (one lane = one episode), directly against the oracle"""
+    stats = KC.check_rollout_episodes(bk, *case)
+    assert stats["sequential_compared"]          # (no knife-edge draw in the replayed episode of any of these cases)
+
+
+@pytest.mark.parametrize("mx", ["1", "0"])       # the identity of the two TD-target routes: within 3e-6 | bit for bit
+@pytest.mark.parametrize("S,N,B,ep,width", [(2, 5, 60, 3, 10), (1, 3, 300, 20, 513), (1, 2, 8, 2, 1), (16, 256, 1000, 20, 512)])
+def test_row_helpers(bk, S, N, B, ep, width, mx, monkeypatch):
+    monkeypatch.setenv("RCMARL_MIDVALUE_MX", mx)
+    KC.check_row_helpers(bk, S, N, B, ep, width)
+
+
 @pytest.mark.parametrize("S,N,B,in_dim,advs,bs,shuffle", [(2, 5, 1000, 10, [4], 32, True), (1, 5, 3000, 15, [1, 3], 32, True),
                                                           (1, 64, 500, 192, [0, 63], 32, True), (1, 256, 200, 768, [7], 32, False),
                                                           (7, 6, 900, 18, [2, 5], 40, True), (9, 5, 333, 20, [0], 7, True),
@@ -311,17 +330,13 @@ def test_wide_consensus_head(bk, S, N, B, in_dim, hid, d, H, graph, f16, wide_fo
 def test_copy3d_more_batches_than_a_grid_dimension(bk):
     """rcmarl_copy3d with more than 65535 batches (AdversaryPath publishes message rows with batches = seeds): the grid's z extent is
     capped and the kernel strides over the rest; masked rows stay untouched."""
-    rng = np.random.default_rng(9)
-    batches, rows, cols, ld = 70001, 3, 8, 12
-    src = rng.normal(size=(batches, rows, ld)).astype(np.float32)
-    dst0 = rng.normal(size=(batches, rows, ld)).astype(np.float32)
-    mask = np.array([1, 0, 1], np.int32)
-    d_src, d_dst, d_mask = bk.dev(src), bk.dev(dst0), bk.dev(mask)
-    bk.lib.rcmarl_copy3d(bk.ptr(d_src), rows * ld, ld, bk.ptr(d_dst), rows * ld, ld, batches, rows, cols, bk.ptr(d_mask), bk.stream)
-    got = bk.host(d_dst)
-    want = dst0.copy()
-    want[:, [0, 2], :cols] = src[:, [0, 2], :cols]
-    np.testing.assert_array_equal(got, want)
+    KC.check_copy3d(bk, "more_batches_than_a_grid_dimension")
+
+
+@pytest.mark.parametrize("case", KC.COPY3D_SMALL)
+def test_copy3d(bk, case):
+    """the 4-byte form (odd columns / strides / base pointers), no mask, an empty mask, the early return, the refused shapes"""
+    KC.check_copy3d(bk, case)
 
 
 # ---- the same layers on pre-split packed operands (hid % 128 == 0): csrc/dense_pk.hip ---------------------------------
