@@ -388,10 +388,13 @@ int rcmarl_pk_supported(int hid);        /* 1: hid % 128 == 0 and the lattice pa
 int rcmarl_layer1_forward_lattice_pk(const void* kp, int kp_rt, int kp_kt, const void* wp, int wp_rt, int wp_kt, const float* theta,
                                      void* a1_bk, int bk_rt, void* a1_kb, int kb_kt, unsigned* s1, int s1_ld, int* ovf_flag, int S, int N,
                                      int B, int in_dim, int hid, int ldp, void* stream);
-/* RANGE.  The pieces saturate instead of overflowing (|a1| > 1015, |W2| or |W2 W3| > 63, |dz1| > 254 are carried clipped, finite).  The
+/* RANGE.  The pieces saturate instead of overflowing (|a1| > 1015, |W2| or |W2 W3| > 63, |dz1| or |dz3| > 254 are carried clipped,
+ * finite; dz3 is what rcmarl_pk_head packs into dzv, and rcmarl_pk_backward_data, which reads the same dz3, raises the flag for it).  The
  * three producers of large operands take an optional `ovf_flag` (one int in device memory, never cleared by the library): set to 1 when
- * a value left the range -- a caller polls it between blocks and switches to the rcmarl_dense_* entry points (which recompute such
- * tiles in fp32) if it matters to it.
+ * a value left the range (a NaN counts) -- a caller polls it between blocks and switches to the rcmarl_dense_* entry points (which
+ * recompute such tiles in fp32) if it matters to it.  The flag is one int for all (seed, agent) rows of a launch; the other rows of a
+ * flagged launch are computed exactly as without it.  What was computed before the poll stays as it is: the engine (rcmarl_amd.engine,
+ * _poll_pk_range) does not redo the block in which the flag rose, only the blocks after it leave the packed form.
  * W2, W3 of theta[s][n] -> w2t, w2w3, rs[k] = sum_j W2[k][j] W3[j] */
 int rcmarl_pk_pack_w2(const float* theta, void* w2t, void* w2w3, float* rs, int* ovf_flag, int S, int N, int in_dim, int hid, int ldp,
                       void* stream);

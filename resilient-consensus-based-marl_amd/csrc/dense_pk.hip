@@ -109,7 +109,9 @@ __global__ __launch_bounds__(256) void k_pk_pack_w2(const float* __restrict__ th
     v += __shfl_xor(v, 2);
     if (c4 == 0) rs[(long)z * hid + rt * 128 + (t >> 2) + 64 * q] = v;
   }
-  if (ovf != nullptr && !(amax * RC_F16_W_SCALE <= 65000.f)) *ovf = 1;     // (|W2| or |W2 W3| > 63: the pieces saturate; NaN counts)
+  // (|W2| or |W2 W3| > 63: the pieces saturate.  A NaN counts: rc_amax3 drops it -- a maximum returns its other operand -- but every
+  // entry of W2 went into the row sums, and those keep it)
+  if (ovf != nullptr && (!(amax * RC_F16_W_SCALE <= 65000.f) || acc[0] != acc[0] || acc[1] != acc[1])) *ovf = 1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -276,7 +278,7 @@ struct PkBdArgs {
   const float* dz3; int ldb;                // [Z][ldb]
   unsigned char* dzp; int dzp_rt, dzp_kt;   // per seed [dzp_rt][dzp_kt][2][8 KiB], rows = agent * hid + unit
   float* gb1part;                           // [Z][ntb][hid]
-  int* ovf;                                 // set when |2^8 dz1| leaves the f16 range
+  int* ovf;                                 // set when |2^8 dz1| or |2^8 dz3| leaves the f16 range
   int Z, N, B, hid, ntb;
 };
 
@@ -298,7 +300,11 @@ __global__ RC_LAT_OCC(T::THREADS, 2) void k_pk_backward_data(const PkBdArgs a) {
   float* sg = sdz + BM;
   if (threadIdx.x < BM) {
     const int b = bm * BM + threadIdx.x;
-    sdz[threadIdx.x] = b < a.B ? a.dz3[(long)z * a.ldb + b] : 0.f;
+    const float d3 = b < a.B ? a.dz3[(long)z * a.ldb + b] : 0.f;
+    sdz[threadIdx.x] = d3;
+    // dz3 itself travels as two f16 pieces of 2^8 dz3 (rcmarl_pk_head -> dzv, the operand of rcmarl_pk_backward_w2) and saturates
+    // there beyond the same bound; with |sum_j W2 W3| < 1 it gets there before dz1 does.  Flagged here: the head takes no flag.
+    if (a.ovf != nullptr && !(fabsf(d3) * RC_F16_DZ_SCALE <= 65000.f)) *a.ovf = 1;
   }
   __syncthreads();
   rc_f16_saturate();

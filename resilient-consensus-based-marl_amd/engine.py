@@ -263,8 +263,11 @@ class RPBCACEngine:
         """Packed operands of the rcmarl_pk_* path (include/rcmarl.h has the layouts): the layer-1 activations of the network a fit /
         the consensus step works on in both orientations + their sign bits (`net`: what step 0 of the next local fit re-uses), a
         second replay-row-major image for value passes, the two packed forms of W2, the layer-2 masks, and the small reduction parts.
-        RCMARL_WIDE_PK=0 keeps the round-4 path (fp32 operands split while they are staged, wide_kernels.hip)."""
+        RCMARL_WIDE_PK=0 keeps the round-4 path (fp32 operands split while they are staged, wide_kernels.hip); so does an engine that
+        has left the packed path for good (_pk_range_fallback, set by _poll_pk_range), however often its row buffers are re-allocated."""
         self.pk = None
+        if self._pk_range_fallback:
+            return
         if not (self.wide and getattr(self, "lat_enabled", False)) or self.hid["critic"] % 128:
             return
         if os.environ.get("RCMARL_WIDE_PK", "1") in ("0", "false"):
@@ -1416,6 +1419,7 @@ class RPBCACEngine:
                 self.rp[k][:, :c.buffer_size] = self.rp[k][:, q:B].clone()
             self.B = c.buffer_size
         self.timers["blocks"] += 1
+        self._poll_pk_range()
 
     def _actor_update(self, B):
         c, L, S, N = self.cfg, self.lib, self.S, self.N
@@ -1528,21 +1532,40 @@ class RPBCACEngine:
 
     _diverged_warned = False
     _shards_synced = False
+    _pk_range_fallback = False                # the packed-operand path was left for good (_poll_pk_range); _init_wide_pk honours it
+
+    def _poll_pk_range(self):
+        """End of every update block of an engine ON the packed-operand path (any other engine returns at once: no device-to-host
+        read, no collective): did a critic operand leave the f16 range of the packed form (|a1| > 1015, |W2| or |W2 W3| > 63,
+        |dz1| or |dz3| > 254)?  Its pieces were carried clipped in the block that just ran -- that block is not redone -- and from the next block
+        on this engine takes the rcmarl_dense_* path for good, whose kernels recompute such tiles in fp32: what the reference's
+        arithmetic does with the same numbers.  The flag covers every (seed, agent) row the kernels touch, a Faulty agent's frozen
+        critic included.  In an agent-sharded instance a rank's flag covers its own agents only and the ranks must take the same
+        path (their collectives pair up by call order): the flag is reduced (MAX) over the shard's communicator, so every rank
+        falls back in the same block -- a COLLECTIVE there, like the finite verdict of _warn_if_diverged."""
+        if self.pk is None:
+            return
+        if self.shard is not None:
+            parts = [torch.empty_like(self.pk.ovf) for _ in range(self.shard.world)]
+            self.shard.comm.all_gather(parts, self.pk.ovf)
+            raised = any(int(p.item()) != 0 for p in parts)
+        else:
+            raised = int(self.pk.ovf.item()) != 0
+        if raised:
+            import warnings
+            warnings.warn("rcmarl_amd: a wide-critic operand left the f16 range of the packed-operand path (weights or activations "
+                          "of some agent's critic, an adversary's frozen one included, grew beyond it; the block that just ran carried "
+                          "them clipped); from the next block on this engine runs the dense path that recomputes out-of-range tiles "
+                          "in fp32", RuntimeWarning)
+            self._pk_range_fallback = True
+            self.pk = None
+            self.a1_cached["critic"] = self.a2_cached = False
 
     def _warn_if_diverged(self):
         """The reference's plain-SGD local fits diverge to NaN when fast_lr is too large for the input width
         (e.g. 0.01 at N = 256); it would carry on silently.  One warning per engine, one reduction per block.  In an
         agent-sharded instance a rank only sees its own agents' rows: the verdict is all-reduced (MIN) over the shard's
         communicator, so every rank warns (or none) -- a COLLECTIVE there."""
-        if self.pk is not None and int(self.pk.ovf.item()) != 0:
-            # a critic operand left the f16 range of the packed-operand path (|a1| > 1015, |W2| or |W2 W3| > 63, |dz1| > 254: a fit that
-            # is blowing up): its pieces were carried clipped.  From here on this engine takes the rcmarl_dense_* path, whose kernels
-            # recompute such tiles in fp32 -- what the reference's arithmetic would do with the same (diverging) numbers.
-            import warnings
-            warnings.warn("rcmarl_amd: a wide-critic operand left the f16 range of the packed-operand path (training is diverging: "
-                          "lower fast_lr); falling back to the dense path that recomputes out-of-range tiles in fp32", RuntimeWarning)
-            self.pk = None
-            self.a1_cached["critic"] = self.a2_cached = False
         if self._diverged_warned:
             return
         finite = all(bool(torch.isfinite(self.theta[k]).all().item()) for k in ("critic", "tr", "actor"))

@@ -34,6 +34,24 @@ def make_inputs(args, nrow, seeds, weight_seed=3, critic_hid=20):
     return W, goals
 
 
+# The packed-operand path of a wide critic (csrc/dense_pk.hip) carries 2^10 W2 as two f16 pieces and raises its flag when that leaves
+# 65000 (csrc/dense_pk.hip, k_pk_pack_w2: `!(amax * RC_F16_W_SCALE <= 65000.f)`), i.e. at |W2| > 63.48.  70 is 1.10 of that bound.
+PK_PLANT_W2 = 70.0
+
+
+def plant_out_of_range_w2(critic, value=PK_PLANT_W2):
+    """ONE entry W2[k][j] = value in a critic [W1, b1, W2, b2, W3, b3] (in place): enough to raise the range flag of the packed-operand
+    path, and the gentlest such trigger -- k is the hidden unit with the smallest sum_c |W1[c][k]| + |b1[k]| (its layer-1 activation
+    is small on every input), j the layer-2 unit with the smallest |W3[j]| (the value moves least), so a1, W2 W3 and dz1 stay in range
+    and the float32 oracle is nowhere near diverging.  Under H >= 1 the entry is the one outlier of its column among the neighbours'
+    messages, so the first hidden-layer consensus trims it away: the flag rises in the first block and the critics are ordinary
+    afterwards.  Returns (k, j)."""
+    k = int(np.argmin(np.abs(critic[0]).sum(axis=0) + np.abs(critic[1])))
+    j = int(np.argmin(np.abs(critic[4][:, 0])))
+    critic[2][k, j] = np.float32(value)
+    return k, j
+
+
 def _oracle_seed_job(payload):
     """one seed of run_oracle in a worker process (spawned: nothing of the parent's GPU state travels)"""
     import os
@@ -576,3 +594,139 @@ def check_block_from_injected_state(args, nrow, ncol, device, lib, seeds, blocks
     eng.update_block()
     eng.sync()
     return eng, network_errors(eng, o_w), o_w
+
+
+def _weight_errors(got, want):
+    """{net: worst |w - w_oracle| / max(1, |w|max) over the agents} for got / want = [agent][actor, critic, tr] parameter lists"""
+    out = {}
+    for k, net in enumerate(("actor", "critic", "tr")):
+        out[net] = max(float(np.abs(a - b).max()) / max(1.0, float(np.abs(b).max()))
+                       for g_i, w_i in zip(got, want) for a, b in zip(g_i[k], w_i[k]))
+    return out
+
+
+def check_pk_range_fallback(device, lib, hid, monkeypatch, tmp_path, planted_label="Cooperative", n=5, nrow=5, max_ep_len=3, n_ep_fixed=2,
+                            n_epochs=2, buffer_size=12, fast_lr=0.01, seed=91, rtol=1e-5, actor_tol=1e-5):
+    """The range fallback of the packed-operand wide-critic path (RPBCACEngine._poll_pk_range) in ONE instance, end to end.
+
+    Scenario: n agents on the circulant d = 4 graph, H = 1, critic width `hid` (a multiple of 128), lattice layer 1, n_epochs >= 2 (so
+    the cached-a2 TD shortcut and _a2_rows_ok run).  The LAST agent -- Cooperative, or a Faulty one whose critic is frozen -- starts
+    with ONE out-of-range operand: W2[k][j] = 70 (the bound is 65000 / 2^10 = 63.48) on the hidden unit k with the smallest layer-1
+    weights and the layer-2 unit j with the smallest |W3| (plant_out_of_range_w2).  That is the gentlest trigger there is: a1, W2 W3
+    and dz1 stay in range, a Cooperative agent's entry is trimmed away by the first hidden-layer consensus (H = 1: it is the one
+    outlier of its column), a Faulty agent's stays in its frozen critic for good and reaches the neighbours only through the trimmed
+    mean.  The reference's fast_lr = 0.01 needs no lowering for it: THE FLOAT32 ORACLE, run from the engine's state on every block of
+    this test, STAYS FINITE WITH NO WEIGHT ABOVE 1e4 (asserted below on the oracle's side: the case cannot pass by both sides diverging).
+
+    Checked: (control) the same scenario without the planted value never warns and stays on the packed path; (flagged block, through
+    run_block(), not train()) ends with the RuntimeWarning -- which does not blame fast_lr: the row may be a frozen adversary's --,
+    eng.pk None, weights finite; (next block) bit-identical to a fresh engine built with RCMARL_WIDE_PK=0 from the same checkpoint,
+    and within `rtol` (critic, team-reward net) / `actor_tol` of oracle.update_block from the identical snapshot, the planted agent
+    included; (sticky) the replay grows past `cap`, every row-sized buffer is re-allocated, the engine stays off the packed path and
+    does not warn again.
+
+    The flagged block itself ran on clipped operands and is not redone (that would cost a copy of every wide weight per block); its
+    deviation from the oracle's block from identical state is printed and returned, not held to a bar.  Measured, worst
+    |w - w_oracle| / max(1, |w|max) over the agents (actor / critic / team-reward net):
+      hipemu, 5 agents, 128 units:  Cooperative 3.9e-7 / 2.2e-7 / 6.0e-8,  Faulty 7.2e-7 / 3.0e-8 / 6.0e-8
+      MI355X, 8 agents, 128 units:  Cooperative 5.5e-7 / 2.2e-7 / 3.0e-8,  Faulty 1.8e-7 / 3.0e-8 / 3.0e-8
+      MI355X, 8 agents, 512 units:  Cooperative 7.6e-7 / 1.8e-7 / 6.0e-8,  Faulty 2.0e-6 / 1.5e-8 / 6.0e-8
+    (one entry clipped from 70 to the largest f16 / 2^10 = 63.97 on a unit with a small activation moves little; the block after it:
+    at most 9e-8 on every network, both backends).
+    Returns {"flagged": errors of the flagged block, "next": errors of the block after it}."""
+    import warnings
+    import pytest
+    assert hid % 128 == 0
+    labels = ["Cooperative"] * (n - 1) + [planted_label]
+    in_nodes = [[(i + k) % n for k in range(4)] for i in range(n)]
+    args = make_args(labels, H=1, n_episodes=0, max_ep_len=max_ep_len, n_ep_fixed=n_ep_fixed, n_epochs=n_epochs, buffer_size=buffer_size,
+                     seed=seed, in_nodes=in_nodes, fast_lr=fast_lr)
+    seeds = (seed,)
+    W, goals = make_inputs(args, nrow, seeds, critic_hid=hid)
+
+    def make(W_):
+        cfg = EngineConfig(n, labels, in_nodes, H=1, gamma=args["gamma"], slow_lr=args["slow_lr"], fast_lr=fast_lr, max_ep_len=max_ep_len,
+                           n_ep_fixed=n_ep_fixed, n_epochs=n_epochs, buffer_size=buffer_size, nrow=nrow, ncol=nrow, n_seeds=1,
+                           rng_mode="device", lattice=True, critic_hid=hid)
+        eng = RPBCACEngine(cfg, seeds=list(seeds), device=device, lib=lib)
+        for i in range(n):
+            for net in ("actor", "critic", "tr"):
+                eng.set_weights(0, i, net, W_[0][i][net])
+        eng.set_goals(np.stack(goals))
+        return eng
+
+    def weights(eng):
+        return [[eng.get_weights(0, i, net) for net in ("actor", "critic", "tr")] for i in range(n)]
+
+    # control: no planted value -> a block on the packed path, no warning
+    ctl = make(W)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        ctl.run_block()
+        assert ctl.pk is not None and not ctl._pk_range_fallback
+    assert ctl.wide and ctl.lat_active and ctl._pk_ok("critic", "s", ctl.lat_B)
+    assert int(ctl.pk.ovf.item()) == 0
+
+    Wp = [[{net: [a.copy() for a in W[0][i][net]] for net in W[0][i]} for i in range(n)]]
+    k, j = plant_out_of_range_w2(Wp[0][n - 1]["critic"])
+    eng = make(Wp)
+    assert eng.pk is not None
+    snaps, update_block = [], eng.update_block
+
+    def update_block_snapped():                     # the state every update block starts from, for the oracle
+        snaps.append(snapshot_for_oracle(eng, 0))
+        return update_block()
+    eng.update_block = update_block_snapped
+    # the block in which the flag rises, through run_block()
+    with pytest.warns(RuntimeWarning, match="packed-operand") as rec:
+        eng.run_block()
+    msgs = [str(w.message) for w in rec if "packed-operand" in str(w.message)]
+    assert len(msgs) == 1 and "fast_lr" not in msgs[0] and "dense path" in msgs[0], msgs
+    assert eng.pk is None and eng._pk_range_fallback and not eng._pk_ok("critic", "s", eng.B)
+    after = {0: weights(eng)}
+    assert all(bool(np.isfinite(a).all()) for ag in after[0] for net in ag for a in net)
+    ck = str(tmp_path / ("pk_fallback_%d_%s.pt" % (hid, planted_label)))
+    eng.save_checkpoint(ck)
+    # the next block: (a) against an engine that never had the packed path, from the same checkpoint
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        eng.run_block()
+        eng.sync()
+        after[1] = weights(eng)
+        monkeypatch.setenv("RCMARL_WIDE_PK", "0")
+        dense = make(W)
+        monkeypatch.delenv("RCMARL_WIDE_PK")
+        assert dense.pk is None
+        dense.load_checkpoint(ck)
+        dense.run_block()
+        dense.sync()
+    assert eng.adam_t == dense.adam_t == 2
+    for net in eng.theta:
+        np.testing.assert_array_equal(eng.theta[net].cpu().numpy(), dense.theta[net].cpu().numpy(), err_msg=net)
+    for net in eng.loss:
+        np.testing.assert_array_equal(eng.loss[net].cpu().numpy(), dense.loss[net].cpu().numpy(), err_msg="loss " + net)
+    np.testing.assert_array_equal(eng.adam_m.cpu().numpy(), dense.adam_m.cpu().numpy())
+    np.testing.assert_array_equal(eng.adam_v.cpu().numpy(), dense.adam_v.cpu().numpy())
+    for key in eng.rp:
+        np.testing.assert_array_equal(eng.rp[key][:, :eng.B].cpu().numpy(), dense.rp[key][:, :dense.B].cpu().numpy())
+    # sticky: the replay grows past cap (a trailing episode, then a second train() call), every row-sized buffer is re-allocated
+    cap0 = eng.cap
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        eng.train(n_ep_fixed + 1)
+        eng.train(n_ep_fixed)
+    assert eng.cap > cap0 and eng.pk is None and eng._pk_range_fallback
+    assert len(snaps) == 4
+    # the oracle, one update block from each of those states
+    o_w = run_oracle_blocks_parallel(dict(args), snaps)
+    for b, ow in enumerate(o_w):
+        big = max(float(np.abs(a).max()) for ag in ow for net in ag[:3] for a in net)
+        assert all(bool(np.isfinite(a).all()) for ag in ow for net in ag[:3] for a in net) and big <= 1e4, \
+            "the ORACLE does not stay finite and below 1e4 in block %d (largest |w| %g): not a case for this check" % (b, big)
+    out = {"flagged": _weight_errors(after[0], o_w[0]), "next": _weight_errors(after[1], o_w[1])}
+    print("[pk range fallback, %s, %d units, planted %s agent W2[%d][%d] = %g, fast_lr %g] worst |w - w_oracle| / max(1,|w|max): flagged block "
+          "(clipped operands, no bar) actor %.2e critic %.2e tr %.2e | next block actor %.2e critic %.2e tr %.2e (bars %.0e / %.0e / %.0e)"
+          % (device, hid, planted_label, k, j, PK_PLANT_W2, fast_lr, out["flagged"]["actor"], out["flagged"]["critic"], out["flagged"]["tr"],
+             out["next"]["actor"], out["next"]["critic"], out["next"]["tr"], actor_tol, rtol, rtol))
+    assert out["next"]["critic"] <= rtol and out["next"]["tr"] <= rtol and out["next"]["actor"] <= actor_tol, out
+    return out

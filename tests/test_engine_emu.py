@@ -80,6 +80,14 @@ def test_engine_wide_critic_on_packed_operands_matches_oracle():
     EC.compare(eng, logs, o_logs, o_w)
 
 
+@pytest.mark.parametrize("planted_label", ["Cooperative", "Faulty"])
+def test_packed_operand_range_fallback(planted_label, monkeypatch, tmp_path):
+    """An operand beyond the f16 range of the packed-operand path in ONE agent's critic (a Cooperative agent's; a Faulty agent's frozen
+    one): the engine leaves the packed path at the end of that block, for good, and the next block is the dense path's bit for bit and
+    the oracle's to 1e-5 (tests/engine_checks.check_pk_range_fallback has the scenario and the measured figures)."""
+    EC.check_pk_range_fallback("cpu", emu_lib(), 128, monkeypatch, tmp_path, planted_label=planted_label)
+
+
 def test_update_block_from_injected_state_matches_oracle():
     """One update block from IDENTICAL state (tests/engine_checks.check_block_from_injected_state): after two blocks and the rollout
     of the third the engine's weights, Adam slots and replay rows go into oracle.update_block (training/train_agents.py:100-153);

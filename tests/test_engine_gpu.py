@@ -250,6 +250,16 @@ def test_engine_wide_critic_with_faulty_agents(n, critic_hid, lattice):
     EC.compare(eng, logs, o_logs, o_w)
 
 
+@pytest.mark.parametrize("critic_hid", [128, 512])
+@pytest.mark.parametrize("planted_label", ["Cooperative", "Faulty"])
+def test_packed_operand_range_fallback(planted_label, critic_hid, monkeypatch, tmp_path):
+    """tests/engine_checks.check_pk_range_fallback on the gfx950 kernels: an out-of-range operand in ONE agent's critic, the block
+    after the fallback bit-identical to the dense path and within 1e-4 of the oracle from identical state (the bar of the wide-critic
+    probed-row checks, check_probed_rows_vs_oracle), the actors within 5 % of an Adam step (compare()'s bar)."""
+    EC.check_pk_range_fallback("cuda", None, critic_hid, monkeypatch, tmp_path, planted_label=planted_label, n=8, nrow=6, max_ep_len=5,
+                               n_ep_fixed=4, n_epochs=2, buffer_size=40, rtol=1e-4, actor_tol=0.05 * 0.002 + 1e-5)
+
+
 def test_engine_wide_critic_cfg5_shape_paths_agree():
     """BASELINE configs[4] shape at an eighth of the agents (128 agents, 512-unit critic, H=32, circulant d=66, 32x32 grid,
     B = 1000..): one training block with layer 1 of the critic on the bf16x3 lattice kernels + the circulant consensus

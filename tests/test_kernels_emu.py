@@ -301,8 +301,14 @@ def test_pk_fit(bk, S, N, B, width, nrow, ncol, hid, steps, masked):
     WC.check_pk_fit(bk, S, N, B, width, nrow, ncol, hid, steps=steps, lr=0.05, masked_agent=masked, tol=1e-6)
 
 
-def test_pk_operands_beyond_the_f16_range_raise_the_flag(bk):
-    WC.check_pk_range_flag(bk)
+@pytest.mark.parametrize("operand", WC.PK_RANGE_OPERANDS)
+def test_pk_operands_beyond_the_f16_range_raise_the_flag(bk, operand):
+    """hid 128, 2 agents, 150 replay rows (two 128-row tiles): the smallest shape rcmarl_pk_supported accepts"""
+    WC.check_pk_range_flag(bk, operand, tol=1e-6)
+
+
+def test_pk_range_flag_is_sticky_counts_nan_and_may_be_null(bk):
+    WC.check_pk_range_flag_is_sticky(bk)
 
 
 @pytest.mark.parametrize("m128", ["0", "1"])

@@ -352,8 +352,16 @@ def test_pk_fit(bk, S, N, B, width, nrow, ncol, hid, steps, masked):
     print("packed-operand fit: worst |w - w_oracle| / max(1, |w|max) = %.2e" % worst)
 
 
-def test_pk_operands_beyond_the_f16_range_raise_the_flag(bk):
-    WC.check_pk_range_flag(bk)
+@pytest.mark.parametrize("S,N,B,width,nrow,ncol,hid,planted", [(1, 2, 150, 2, 5, 5, 128, (0, 1)), (2, 3, 333, 3, 7, 9, 512, (1, 2))])
+@pytest.mark.parametrize("operand", WC.PK_RANGE_OPERANDS)
+def test_pk_operands_beyond_the_f16_range_raise_the_flag(bk, operand, S, N, B, width, nrow, ncol, hid, planted):
+    """the emulation's shape, and 512 units with B not a multiple of 256 and the planted agent the last of the second seed"""
+    WC.check_pk_range_flag(bk, operand, S, N, B, width, nrow, ncol, hid, planted, tol=1e-5)
+
+
+@pytest.mark.parametrize("N,B,hid", [(2, 150, 128), (3, 333, 512)])
+def test_pk_range_flag_is_sticky_counts_nan_and_may_be_null(bk, N, B, hid):
+    WC.check_pk_range_flag_is_sticky(bk, N=N, B=B, hid=hid)
 
 
 @pytest.mark.parametrize("m128", ["0", "1"])

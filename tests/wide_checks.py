@@ -259,28 +259,29 @@ def pk_encode(bk, pb, d_x, x_stride, d_alpha, S, B, in_dim):
                                  g.ktp[0], g.ktp[1], bk.ptr(pb.flag), bk.stream)
 
 
-def pk_forward(bk, pb, d_alpha, d_theta, S, N, B, in_dim, hid, ldp, ldb, split=True, fit=True, want_a2=False):
-    """layer 1 (lattice GEMM, packed outputs) + pack of W2 + layer 2 (masks / value parts / fp32 a2)"""
+def pk_forward(bk, pb, d_alpha, d_theta, S, N, B, in_dim, hid, ldp, ldb, split=True, fit=True, want_a2=False, ovf=True):
+    """layer 1 (lattice GEMM, packed outputs) + pack of W2 + layer 2 (masks / value parts / fp32 a2); ovf=False: no range flag (NULL)"""
     g, L = pb.g, bk.lib
+    p_ovf = bk.ptr(pb.ovf) if ovf else None
     if split:
         L.rcmarl_w1_split(bk.ptr(d_theta), bk.ptr(d_alpha), bk.ptr(pb.wp), S, N, in_dim, hid, ldp, g.wp[0], g.wp[1], bk.stream)
     L.rcmarl_layer1_forward_lattice_pk(bk.ptr(pb.kp), g.kp[0], g.kp[1], bk.ptr(pb.wp), g.wp[0], g.wp[1], bk.ptr(d_theta),
                                        bk.ptr(pb.a1_bk), pb.bk_rt, bk.ptr(pb.a1_kb) if fit else None, pb.kb_kt,
-                                       bk.ptr(pb.s1) if fit else None, pb.Bp // 32, bk.ptr(pb.ovf), S, N, B, in_dim, hid, ldp, bk.stream)
-    L.rcmarl_pk_pack_w2(bk.ptr(d_theta), bk.ptr(pb.w2t), bk.ptr(pb.w2w3), bk.ptr(pb.rs), bk.ptr(pb.ovf), S, N, in_dim, hid, ldp, bk.stream)
+                                       bk.ptr(pb.s1) if fit else None, pb.Bp // 32, p_ovf, S, N, B, in_dim, hid, ldp, bk.stream)
+    L.rcmarl_pk_pack_w2(bk.ptr(d_theta), bk.ptr(pb.w2t), bk.ptr(pb.w2w3), bk.ptr(pb.rs), p_ovf, S, N, in_dim, hid, ldp, bk.stream)
     L.rcmarl_pk_forward2(bk.ptr(pb.w2t), bk.ptr(pb.a1_bk), pb.bk_rt, bk.ptr(d_theta), bk.ptr(pb.a2) if want_a2 else None,
                          bk.ptr(pb.mask_bj) if fit else None, pb.bk_rt, bk.ptr(pb.mask_jb) if fit else None, pb.kb_kt,
                          bk.ptr(pb.vpart), bk.ptr(pb.npart) if want_a2 else None, S, N, B, in_dim, hid, ldp, ldb, bk.stream)
 
 
-def pk_fit_step(bk, pb, d_alpha, d_msg, d_y, d_mask, d_loss, S, N, B, in_dim, hid, ldp, ldb, lr, split, emit_wp=True):
+def pk_fit_step(bk, pb, d_alpha, d_msg, d_y, d_mask, d_loss, S, N, B, in_dim, hid, ldp, ldb, lr, split, emit_wp=True, ovf=True):
     """one full-batch SGD step of fit() on the packed-operand path (the sequence engine._local_fit_wide_pk runs)"""
     g, L = pb.g, bk.lib
-    pk_forward(bk, pb, d_alpha, d_msg, S, N, B, in_dim, hid, ldp, ldb, split=split)
+    pk_forward(bk, pb, d_alpha, d_msg, S, N, B, in_dim, hid, ldp, ldb, split=split, ovf=ovf)
     L.rcmarl_pk_head(bk.ptr(pb.vpart), bk.ptr(d_msg), bk.ptr(d_y), 0.0, 2, bk.ptr(pb.dz3), bk.ptr(pb.dzv), bk.ptr(pb.losspart), S, N, B,
                      in_dim, hid, ldp, ldb, bk.stream)
     L.rcmarl_pk_backward_data(bk.ptr(pb.mask_bj), pb.bk_rt, bk.ptr(pb.w2w3), bk.ptr(pb.rs), bk.ptr(pb.s1), pb.Bp // 32, bk.ptr(pb.dz3),
-                              bk.ptr(pb.dzp), g.dzp[0], g.dzp[1], bk.ptr(pb.gb1part), bk.ptr(pb.ovf), S, N, B, hid, ldb, bk.stream)
+                              bk.ptr(pb.dzp), g.dzp[0], g.dzp[1], bk.ptr(pb.gb1part), bk.ptr(pb.ovf) if ovf else None, S, N, B, hid, ldb, bk.stream)
     L.rcmarl_pk_backward_w2(bk.ptr(pb.a1_kb), pb.kb_kt, bk.ptr(pb.mask_jb), pb.kb_kt, bk.ptr(pb.dzv), bk.ptr(d_msg), bk.ptr(d_mask),
                             bk.ptr(pb.gw3part), bk.ptr(pb.q), S, N, B, in_dim, hid, ldp, lr, bk.stream)
     L.rcmarl_layer1_backward_sgd_lattice(bk.ptr(pb.ktp), g.ktp[0], g.ktp[1], bk.ptr(pb.dzp), g.dzp[0], g.dzp[1], bk.ptr(d_alpha),
@@ -404,19 +405,206 @@ def check_pk_fit(bk, S, N, B, width, nrow, ncol, hid, steps=2, lr=0.01, masked_a
     return worst
 
 
-def check_pk_range_flag(bk, S=1, N=2, B=150, width=2, nrow=5, ncol=5, hid=128):
-    """Operands beyond the f16 range of the packed form: the pieces saturate (finite outputs) and the producers raise the caller's flag
-    -- W2 of one agent scaled so that 2^10 |W2| > 65000 trips rcmarl_pk_pack_w2, a huge b1 trips the layer-1 epilogue."""
+# The range of the packed form.  The producers compare the SCALED operand with 65000 (just inside the largest f16, 65504) and the scales
+# are fixed: 2^10 for W2 and W2 W3 (csrc/rcmarl_lattice.h RC_F16_W_SCALE, mirrored as lattice.F16_W_SCALE; the comparison is
+# csrc/dense_pk.hip k_pk_pack_w2 `!(amax * RC_F16_W_SCALE <= 65000.f)`), 2^8 for dz1 (RC_F16_DZ_SCALE = lattice.F16_DZ_SCALE;
+# k_pk_backward_data `!(amax <= 65000.f)` on the scaled values) and for dz3, which rcmarl_pk_head packs at the same scale for
+# rcmarl_pk_backward_w2 and k_pk_backward_data checks as it loads it (`!(fabsf(d3) * RC_F16_DZ_SCALE <= 65000.f)`), 2^6 for a1 (RC_F16_ACT_SCALE, csrc/rcmarl_lattice.h -- not mirrored in
+# lattice.py; csrc/lattice_gemm.hip layer-1 epilogue `!(amax * RC_F16_ACT_SCALE <= 65000.f)`).
+PK_RANGE_LIMIT = 65000.0
+PK_ACT_SCALE = 64.0
+
+
+def pk_range_bounds():
+    """largest in-range magnitude per operand: a1 1015.6, W2 and W2 W3 63.48, dz1 and dz3 253.9"""
+    from rcmarl_amd import lattice as LT
+    w, dz = PK_RANGE_LIMIT / LT.F16_W_SCALE, PK_RANGE_LIMIT / LT.F16_DZ_SCALE
+    return {"a1": PK_RANGE_LIMIT / PK_ACT_SCALE, "w2": w, "w2w3": w, "dz1": dz, "dz3": dz}
+
+
+def _ref_dz1(p, x, y):
+    """dz1 [B][hid] of the oracle's full-batch MSE fit (M.fit_mse: dL/dv = 2 (v - y) / B), float32, and v"""
+    v, (x_, z1, a1, z2, a2) = M.forward(p, x, want_cache=True)
+    dout = (np.float32(2.0 / x.shape[0]) * (v - y.reshape(v.shape))).astype(np.float32)
+    dz2 = (dout @ p[4].T) * M.lrelu_grad(z2)
+    return (dz2 @ p[2].T) * M.lrelu_grad(z1), v
+
+
+def _pk_plant(operand, magnitude, p, x, y, rng):
+    """Put ONE value of the given magnitude into operand `operand` of the network p (in place; for dz1 into the targets y [B]) so that
+    it is the largest of that operand; returns the largest magnitude the float32 reference then sees in it."""
+    hid = p[2].shape[0]
+    k, j = int(rng.integers(hid)), int(rng.integers(hid))
+    if operand == "a1":
+        # unit k: its bias lifts the largest pre-activation over the replay rows to `magnitude` (rows beyond B see b1 alone: smaller)
+        k = int(np.argmax((x @ p[0]).max(axis=0)))
+        top = float((x @ p[0][:, k]).max())
+        assert top > 0
+        p[1][k] = np.float32(magnitude - top)
+        # (its outgoing weights 2^-10 of Glorot's: an activation of 1000 through weights of 0.1 would put +-100 into every layer-2 unit,
+        # and the value -- 512 such terms cancelling to a few units -- would be lost in the float32 reference's own rounding)
+        p[2][k, :] *= np.float32(1.0 / 1024.0)
+        z1 = x @ p[0] + p[1]
+        return float(np.abs(np.where(z1 > 0, z1, np.float32(0.1) * z1)).max())
+    if operand == "w2":
+        p[2][k, j] = np.float32(-magnitude)
+        assert np.abs(p[2] * p[4][:, 0]).max() < 0.5 * magnitude          # (it is W2 that trips the flag, not the product)
+        return float(np.abs(p[2]).max())
+    if operand == "w2w3":
+        # |W2| = |W3| = sqrt(magnitude) are each inside the bound (63.48) up to a product of 4029; only their product leaves it
+        p[2][k, j] = np.float32(np.sqrt(magnitude))
+        p[4][j, 0] = np.float32(-magnitude) / p[2][k, j]
+        assert max(np.abs(p[2]).max(), np.abs(p[4]).max()) < 0.9 * 63.47
+        return float(np.abs(p[2] * p[4][:, 0]).max())
+    B = x.shape[0]
+    if operand == "dz3":
+        # one replay row with a large target: dz3[b] = 2 (v - y)[b] / B; dz1 = dz3 t with |t| = |sum_j W2 W3 mask| ~ 0.1 stays far inside
+        b = int(rng.integers(B))
+        v = M.forward(p, x)[:, 0]
+        y[b] = np.float32(v[b] - magnitude * B / 2.0)
+        dz1, v = _ref_dz1(p, x, y)
+        assert magnitude > 1e4 or np.abs(dz1).max() < 0.5 * magnitude            # (it is dz3 that trips the flag, not dz1)
+        return float(np.abs(np.float32(2.0 / B) * (v[:, 0] - y)).max())
+    assert operand == "dz1"
+    # dz1[b][k] = dz3[b] t[b][k] g1: for dz1 to reach its bound while dz3 (same scale, same bound) stays inside, some |t| must exceed 1 --
+    # one pair W2[k][j] = 4, W3[j] = 1.5 (both ordinary sizes) gives |t[b][k]| of 6 on the rows where unit j is active, 0.6 elsewhere
+    # (a pair whose two units are both active on some replay row: the first of a few random draws)
+    w2_kj, w3_j, y1 = p[2].copy(), p[4].copy(), y - np.float32(1.0)
+    for _ in range(16):
+        p[2][...], p[4][...] = w2_kj, w3_j
+        k, j = int(rng.integers(hid)), int(rng.integers(hid))
+        p[2][k, j] = np.float32(4.0)
+        p[4][j, 0] = np.float32(1.5)
+        unit_b = np.abs(_ref_dz1(p, x, y1)[0] - _ref_dz1(p, x, y)[0]).max(axis=1) * np.float32(B / 2.0)  # max_k |d dz1[b][k] / d dz3[b]|
+        b = int(np.argmax(unit_b))
+        if unit_b[b] > 3.0:
+            break
+    assert unit_b[b] > 3.0, unit_b[b]
+    v = M.forward(p, x)[:, 0]
+    y[b] = np.float32(v[b] - (magnitude / unit_b[b]) * B / 2.0)
+    dz1, v = _ref_dz1(p, x, y)
+    dz3 = np.float32(2.0 / B) * (v[:, 0] - y)
+    assert magnitude > 1e4 or np.abs(dz3).max() < 0.55 * magnitude, np.abs(dz3).max()      # (dz3 stays inside at 0.98 and 1.05 of the bound)
+    return float(np.abs(dz1).max())
+
+
+def _pk_launch(bk, x, alpha, params, yv, S, N, B, in_dim, hid, ldp, ldb, lr, pb=None, ovf=True):
+    """One forward pass (every output) and, from the same weights, one fit step.  Returns (outputs per (seed, agent) [Z][...], the
+    flag after the forward pass, the flag after the fit step, buffers)."""
+    theta = pack_rows(params, ldp)
+    d_x, d_al, d_th, d_msg, d_y = bk.dev(x), bk.dev(alpha), bk.dev(theta), bk.dev(theta.copy()), bk.dev(yv)
+    d_mask, d_loss, d_v = bk.dev(np.ones(N, np.int32)), bk.dev(np.zeros((S, N), np.float32)), bk.dev(np.zeros((S, N, ldb), np.float32))
+    pb = PkBuffers(bk, S, N, B, in_dim, hid) if pb is None else pb
+    Z = S * N
+    pk_encode(bk, pb, d_x, B * in_dim, d_al, S, B, in_dim)
+    pk_forward(bk, pb, d_al, d_th, S, N, B, in_dim, hid, ldp, ldb, want_a2=True, ovf=ovf)
+    bk.lib.rcmarl_pk_head(bk.ptr(pb.vpart), bk.ptr(d_th), None, 0.0, 0, bk.ptr(d_v), None, None, S, N, B, in_dim, hid, ldp, ldb, bk.stream)
+    out = {k: np.array(bk.host(getattr(pb, k))).reshape(Z, -1) for k in ("a1_bk", "a1_kb", "s1", "mask_bj", "mask_jb", "a2")}
+    # (the value parts are [Z][rcmarl_pk_parts(hid)][ldb]: one part per tile of units, 128 or 256 wide; the buffer is sized for 128)
+    out["vpart"] = np.array(bk.host(pb.vpart)).reshape(-1)[:Z * bk.lib.rcmarl_pk_parts(hid) * ldb].reshape(Z, -1)
+    out["v"] = np.array(bk.host(d_v)).reshape(Z, -1)[:, :B]
+    assert bk.host(pb.flag)[0] == 0
+    flag_fwd = int(bk.host(pb.ovf)[0])
+    pk_fit_step(bk, pb, d_al, d_msg, d_y, d_mask, d_loss, S, N, B, in_dim, hid, ldp, ldb, lr, split=True, ovf=ovf)
+    out["msg"], out["loss"] = np.array(bk.host(d_msg)).reshape(Z, -1), np.array(bk.host(d_loss)).reshape(Z, -1)
+    return out, flag_fwd, int(bk.host(pb.ovf)[0]), pb
+
+
+def _pk_agent_vs_reference(out, zi, p0, x, y, B, in_dim, hid, pb, lr, tol, knife_tol=1e-3):
+    """The bars of check_pk_forward (3e-6 / 6e-6 / 8e-6) and check_pk_fit (tol, or a proven knife edge) for ONE agent of a launch, against
+    the same float32 statements; every error relative to the largest reference value (rel_close)."""
+    from rcmarl_amd import lattice as LT
+    z1 = x @ p0[0] + p0[1]
+    w1 = np.where(z1 > 0, z1, np.float32(0.1) * z1)
+    z2 = w1 @ p0[2] + p0[3]
+    w2 = np.where(z2 > 0, z2, np.float32(0.1) * z2)
+    dec = LT.pk_unpack(out["a1_bk"][zi].view(np.uint16), B, hid, pb.JK, 2, f16=True)
+    rel_close((dec[0] + dec[1]) / 64.0, w1, 3e-6, "a1_bk")
+    dect = LT.pk_unpack(out["a1_kb"][zi].view(np.uint16), hid, B, pb.kb_kt, 2, f16=True)
+    np.testing.assert_array_equal(dect[0], dec[0].T)
+    np.testing.assert_array_equal(dect[1], dec[1].T)
+    rel_close(out["a2"][zi].reshape(hid, -1)[:, :B].T, w2, 6e-6, "layer-2 activations")
+    rel_close(out["v"][zi], M.forward(p0, x)[:, 0], 8e-6, "value")
+    pw = M.copy_params(p0)
+    hist = M.fit_mse(pw, x, y[:B, None], lr, epochs=1)
+    got = unpack_row(out["msg"][zi], in_dim, 1, hid)
+    err = max(float(np.max(np.abs(got[k] - pw[k])) / max(1.0, float(np.max(np.abs(pw[k]))))) for k in range(6))
+    if err > tol:
+        ratio = knife_edge_ratio(p0, x, y[:B, None], lr, 1)
+        assert ratio < 2e-7 and err <= knife_tol, "fit step of the planted agent: error %.2e beyond %.1e without a knife edge (%.1e)" % (err, tol, ratio)
+    assert abs(out["loss"][zi, 0] - hist[0]) <= 1e-5 * max(1.0, abs(hist[0])), (out["loss"][zi, 0], hist[0])
+    return err
+
+
+PK_RANGE_OPERANDS = ("a1", "w2", "w2w3", "dz1", "dz3")
+
+
+def check_pk_range_flag(bk, operand, S=1, N=2, B=150, width=2, nrow=5, ncol=5, hid=128, planted=(0, 1), lr=0.01, tol=2e-5):
+    """The range contract of the three producers of the packed form, for ONE operand: a1 (layer-1 epilogue of
+    rcmarl_layer1_forward_lattice_pk), W2 or W2 W3 (rcmarl_pk_pack_w2), dz1 or dz3 (rcmarl_pk_backward_data, through one fit step with
+    one large target; dz3 is the head's output, packed at the scale of dz1 for rcmarl_pk_backward_w2).  ONE (seed, agent) = `planted` carries one value of 0.98 / 1.05 / 2000 times the bound (W2 W3: 50 times, the most two in-range factors give) (pk_range_bounds: from the
+    scales in the source, not measured):
+      inside  (0.98): the flag stays 0 and the planted agent meets the bars of check_pk_forward / check_pk_fit against the same float32
+              statements -- a kernel that clips early, or compares with a smaller number, fails here;
+      outside (1.05 and far): the flag is 1 -- after the forward pass for a1 / W2 / W2 W3, only after the fit step for dz1 / dz3 -- and every
+              output is finite (the pieces saturate);
+      always: every OTHER (seed, agent) of the launch is bit-identical, output by output, to the launch without the planted value.
+
+    (The dz1 case of this check is how dz3 came to be an operand of the table: with Glorot weights |sum_j W2 W3| is well below 1, so a
+    growing target drives dz3 out of the range of its packed form before dz1 -- at max |dz1| = 0.98 of the bound 2^8 |dz3| was 353488
+    -- and nothing flagged it: the fit step ended 6.4e-1 (128 units) / 7.9e-1 (512 units) from M.fit_mse with the flag at 0.
+    k_pk_backward_data now checks dz3 as it loads it.  The dz1 case therefore carries one pair W2[k][j] W3[j] = 6, so that dz1 reaches
+    its bound with dz3 at a third of it.)"""
+    bound = pk_range_bounds()[operand]
     rng, in_dim, g, ldp, ldb, params, x, alpha = _wide_lattice_case(S, N, B, width, nrow, ncol, hid, 3)
-    for which in ("w2", "b1"):
+    yv = rng.normal(size=(S, N, ldb)).astype(np.float32)
+    ps, pn = planted
+    zi = ps * N + pn
+    geo = (S, N, B, in_dim, hid, ldp, ldb, lr)
+    clean, f0, f1, _ = _pk_launch(bk, x, alpha, params, yv, *geo)
+    assert (f0, f1) == (0, 0)
+    others = [z for z in range(S * N) if z != zi]
+    assert others
+    for factor in (0.98, 1.05, 50.0 if operand == "w2w3" else 2000.0):
         p2 = [[M.copy_params(p) for p in row] for row in params]
-        if which == "w2":
-            p2[0][1][2] *= np.float32(2000.0)
+        y2 = yv.copy()
+        seen = _pk_plant(operand, factor * bound, p2[ps][pn], x[ps], y2[ps, pn, :B], np.random.default_rng(int(factor * 100) + hid))
+        assert abs(seen / bound - factor) <= 0.005 * factor, (operand, factor, seen / bound)          # the reference sees what was planted
+        out, f_fwd, f_fit, pb = _pk_launch(bk, x, alpha, p2, y2, *geo)
+        print("packed-operand range, %s x %.4g of %.5g (%d units): flag %d after the forward pass, %d after the fit step"
+              % (operand, seen / bound, bound, hid, f_fwd, f_fit))
+        for key in out:
+            np.testing.assert_array_equal(out[key][others], clean[key][others], err_msg="%s x %g: %s of the OTHER agents" % (operand, factor, key))
+        if factor < 1:
+            assert (f_fwd, f_fit) == (0, 0), (operand, factor, f_fwd, f_fit)
+            _pk_agent_vs_reference(out, zi, p2[ps][pn], x[ps], y2[ps, pn], B, in_dim, hid, pb, lr, tol)
         else:
-            p2[0][0][1] += np.float32(5000.0)
-        d_x, d_al, d_th = bk.dev(x), bk.dev(alpha), bk.dev(pack_rows(p2, ldp))
-        pb = PkBuffers(bk, S, N, B, in_dim, hid)
-        pk_encode(bk, pb, d_x, B * in_dim, d_al, S, B, in_dim)
-        pk_forward(bk, pb, d_al, d_th, S, N, B, in_dim, hid, ldp, ldb, want_a2=True)
-        assert bk.host(pb.ovf)[0] == 1, which
-        assert np.isfinite(bk.host(pb.a2)).all() and np.isfinite(bk.host(pb.vpart)).all()
+            assert (f_fwd, f_fit) == ((0, 1) if operand in ("dz1", "dz3") else (1, 1)), (operand, factor, f_fwd, f_fit)
+            for key in out:
+                assert np.isfinite(out[key]).all(), key
+    return bound
+
+
+def check_pk_range_flag_is_sticky(bk, S=1, N=2, B=150, width=2, nrow=5, ncol=5, hid=128, lr=0.01):
+    """"NaN counts" (csrc/dense_pk.hip, k_pk_pack_w2): one NaN in W2 raises the flag.  The library never clears it (include/rcmarl.h,
+    RANGE): an in-range launch on the same flag leaves it at 1.  ovf_flag = NULL is accepted and changes no output.
+
+    (This check found that a NaN did NOT count: rc_amax3 -- v_max3_f32 on the GPU, fmaxf on the emulation -- returns its other operand
+    when one is a NaN, so the running maximum never became one.  k_pk_pack_w2 now also looks at its row sums, which keep a NaN.)"""
+    rng, in_dim, g, ldp, ldb, params, x, alpha = _wide_lattice_case(S, N, B, width, nrow, ncol, hid, 3)
+    yv = rng.normal(size=(S, N, ldb)).astype(np.float32)
+    geo = (S, N, B, in_dim, hid, ldp, ldb, lr)
+    p2 = [[M.copy_params(p) for p in row] for row in params]
+    p2[S - 1][N - 1][2][hid // 2, 3] = np.float32(np.nan)
+    _, f_fwd, f_fit, pb = _pk_launch(bk, x, alpha, p2, yv, *geo)
+    assert (f_fwd, f_fit) == (1, 1)
+    clean, f_fwd, f_fit, _ = _pk_launch(bk, x, alpha, params, yv, *geo, pb=pb)          # same buffers, same flag, in-range operands
+    assert (f_fwd, f_fit) == (1, 1)
+    ref, f_fwd, f_fit, _ = _pk_launch(bk, x, alpha, params, yv, *geo)
+    assert (f_fwd, f_fit) == (0, 0)
+    for key in ref:                                                                      # (and the NaN left nothing behind in them)
+        np.testing.assert_array_equal(clean[key], ref[key], err_msg=key)
+    nul, f_fwd, f_fit, _ = _pk_launch(bk, x, alpha, params, yv, *geo, ovf=False)
+    assert (f_fwd, f_fit) == (0, 0)
+    for key in ref:
+        np.testing.assert_array_equal(nul[key], ref[key], err_msg="ovf_flag = NULL: " + key)
