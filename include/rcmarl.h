@@ -60,6 +60,28 @@ int rcmarl_consensus_params_circulant_supported(int N, int d, int H);
 int rcmarl_consensus_params_circulant(const float* msg, float* theta, const int* coop, int S, int N, int ldp, int P_hid,
                                       int d, int H, float* lo_dbg, float* hi_dbg, void* stream);
 
+/* K1 on an IRREGULAR in-graph: every agent its own in-neighbourhood size d_i and trim parameter H_i
+ * (RPBCAC_agent(..., H=...) is per agent and _resilient_aggregation sorts whatever list it is handed,
+ * agents/resilient_CAC_agents.py:42-58; training/train_agents.py:129-130 indexes in_nodes[i], a list of lists).
+ * The graph is CSR: nbr_off int[N+1], nbr_idx int[nbr_off[N]] with nbr_idx[nbr_off[i]] == i.  order int[n_coop] lists the
+ * COOPERATIVE agents sorted by their (d, H) class; classes[q] = {d, H, first, count} says that order[first .. first+count)
+ * are the agents of class q (every listed agent has nbr_off[i+1] - nbr_off[i] == d; 2H+1 <= d <= N).  `classes` is HOST
+ * memory, read during the call only; everything else is device memory.  All classes run in ONE launch (up to 32 classes;
+ * one launch per 32 beyond): the message matrix is read once.  Rows of agents not in order[] and columns >= P_hid are
+ * not written.  An agent's result has the bits rcmarl_consensus_params gives on a regular graph of its class when
+ * d <= 20 or no selection network is generated for (d, H); the few generated networks with d > 20 are not compiled
+ * into this kernel (rank counting instead: same values, a zero's sign may differ among tied +-0).
+ * RCMARL_ERR_UNSUPPORTED when the [N][4] tile image exceeds the LDS, as rcmarl_consensus_params. */
+typedef struct rcmarl_ragged_class {
+  int d, H;                                /* in-neighbourhood size (own value included) and trim parameter of the class */
+  int first, count;                        /* its agents: order[first .. first + count) */
+} rcmarl_ragged_class;
+int rcmarl_ragged_class_layout(int what);              /* sizeof(rcmarl_ragged_class) (what = 0) / offset of field `what` (1 = H, 2 = first,
+                                                        * 3 = count), -1 otherwise */
+int rcmarl_consensus_params_ragged(const float* msg, float* theta, const int* nbr_off, const int* nbr_idx, const int* order,
+                                   const rcmarl_ragged_class* classes, int n_classes, int S, int N, int ldp, int P_hid,
+                                   float* lo_dbg, float* hi_dbg, void* stream);
+
 /* K4 layer 1 forward (shared input => one GEMM per seed), Keras Dense + LeakyReLU(0.1):
  * a1t[s][n*hid+j][b] = lrelu(sum_k x[s][b][k]*W1[s][n][k][j] + b1[s][n][j]).
  * Replaces the first Dense of every model call at agents/resilient_CAC_agents.py:66,79,95-97,114,181,201. */
@@ -184,6 +206,14 @@ int rcmarl_mid_value_f32(const float* a1t, const float* theta, const float* r_ap
 int rcmarl_consensus_head(const float* a1t, const float* theta, const float* msg, const int* nbr,
                           const int* coop, float* partials, float* agg_out, int S, int N, int B, int in_dim,
                           int hid, int ldp, int ldb, int d, int H, void* stream);
+/* K2+K3 on an irregular in-graph (graph, order[] and classes as rcmarl_consensus_params_ragged): one launch per class,
+ * workgroup column y of class q works on agent order[first + y]; per class the kernel rcmarl_consensus_head picks for
+ * (d, H) -- and the chunking it picks for S x N networks -- so an agent's records and aggregates have the bits of that
+ * call on a regular graph of its class.  Records of agents not in order[] are not written. */
+int rcmarl_consensus_head_ragged(const float* a1t, const float* theta, const float* msg, const int* nbr_off,
+                                 const int* nbr_idx, const int* order, const rcmarl_ragged_class* classes, int n_classes,
+                                 float* partials, float* agg_out, int S, int N, int B, int in_dim, int hid, int ldp, int ldb,
+                                 void* stream);
 /* K3 alone: the same projection residual toward a caller-supplied aggregate agg[S][N][ldb]
  * (critic_update_team(s, agg) / TR_update_team(sa, agg) called on their own, :60-84). */
 int rcmarl_projection_residual(const float* a1t, const float* theta, const float* agg, const int* coop,

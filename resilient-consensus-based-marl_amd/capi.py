@@ -18,6 +18,13 @@ class MbJob(C.Structure):
     _fields_ = [("x", C.c_void_p), ("x_seed_stride", C.c_long), ("theta", C.c_void_p), ("agents", C.c_void_p), ("n_adv", C.c_int),
                 ("in_dim", C.c_int), ("ldp", C.c_int), ("reserved_", C.c_int), ("y", C.c_void_p), ("perm", C.c_void_p),
                 ("loss_out", C.c_void_p), ("ovf_flags", C.c_void_p)]
+
+
+class RaggedClass(C.Structure):
+    """rcmarl_ragged_class (include/rcmarl.h): one (d, H) class of the ragged consensus entry points"""
+    _fields_ = [("d", C.c_int), ("H", C.c_int), ("first", C.c_int), ("count", C.c_int)]
+
+
 c_f64p = C.c_void_p      # double*
 c_stream = C.c_void_p    # hipStream_t
 
@@ -45,6 +52,13 @@ SIGNATURES = {
     # msg, theta, coop, S, N, ldp, P_hid, d, H, lo_dbg, hi_dbg, stream
     "rcmarl_consensus_params_circulant": [c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32p, c_f32p,
                                           c_stream],
+    "rcmarl_ragged_class_layout": [c_int],
+    # msg, theta, nbr_off, nbr_idx, order, classes (host array of RaggedClass), n_classes, S, N, ldp, P_hid, lo_dbg, hi_dbg, stream
+    "rcmarl_consensus_params_ragged": [c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                       c_f32p, c_f32p, c_stream],
+    # a1t, theta, msg, nbr_off, nbr_idx, order, classes (host), n_classes, partials, agg_out, S, N, B, in_dim, hid, ldp, ldb, stream
+    "rcmarl_consensus_head_ragged": [c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p, c_int, c_f32p, c_f32p, c_int,
+                                     c_int, c_int, c_int, c_int, c_int, c_int, c_stream],
     # x, x_seed_stride, theta, a1t, S, N, B, in_dim, hid, ldp, ldb, stream
     "rcmarl_layer1_forward": [c_f32p, c_long, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_stream],
@@ -204,7 +218,7 @@ SIGNATURES = {
     # src, src_batch, ld_src, dst, dst_batch, ld_dst, batches, rows, cols, row_mask, stream
     "rcmarl_copy3d": [c_f32p, c_long, c_long, c_f32p, c_long, c_long, c_int, c_int, c_int, c_i32p, c_stream],
 }
-UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_lattice_forget", "rcmarl_fit_partial_size", "rcmarl_lattice_set_f16_mode",  "rcmarl_actor_partial_size", "rcmarl_rows_per_chunk", "rcmarl_lattice_f16_mode",
+UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_layout", "rcmarl_lattice_forget", "rcmarl_fit_partial_size", "rcmarl_lattice_set_f16_mode",  "rcmarl_actor_partial_size", "rcmarl_rows_per_chunk", "rcmarl_lattice_f16_mode",
              "rcmarl_wide_grad_size", "rcmarl_wide_rows_per_chunk", "rcmarl_wide_f16_mode", "rcmarl_wide_set_f16_mode",
              "rcmarl_consensus_params_circulant_supported", "rcmarl_pk_supported", "rcmarl_pk_parts"}
 

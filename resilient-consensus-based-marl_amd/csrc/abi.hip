@@ -25,6 +25,17 @@ RCMARL_EXPORT int rcmarl_mb_job_layout(int what) {
   }
 }
 
+// sizeof(rcmarl_ragged_class) (what = 0) or the offset of its field number `what` (1 H, 2 first, 3 count), -1 otherwise
+RCMARL_EXPORT int rcmarl_ragged_class_layout(int what) {
+  switch (what) {
+    case 0: return (int)sizeof(rcmarl_ragged_class);
+    case 1: return (int)offsetof(rcmarl_ragged_class, H);
+    case 2: return (int)offsetof(rcmarl_ragged_class, first);
+    case 3: return (int)offsetof(rcmarl_ragged_class, count);
+    default: return -1;
+  }
+}
+
 namespace {
 std::mutex g_mu;
 int g_mode = -1;                                         // -1: not read yet

@@ -421,6 +421,28 @@ size_t circ_smem(int N, int d, int G, int TC) { return 2 * ((size_t)(N + d + G -
 
 // Any (d, H) without a generated network: order statistics by rank counting
 // out of the LDS tile (O(d^2) LDS reads).  Correct for every d >= 2H+1; slow.
+// One agent, one column: nb = the agent's neighbour list, c = the lane's column of the [N][TC] tile.
+__device__ __forceinline__ float aggregate_rank_count(const float* tile, const int* nb, int log2tc, int c, int d, int H,
+                                                      float& lower, float& upper) {
+  const float own = tile[(nb[0] << log2tc) + c];
+  float lo = own, hi = own;
+  for (int k = 0; k < d; ++k) {
+    const float x = tile[(nb[k] << log2tc) + c];
+    int rank = 0;
+    for (int m = 0; m < d; ++m) {
+      const float y = tile[(nb[m] << log2tc) + c];
+      rank += (y < x || (y == x && m < k)) ? 1 : 0;
+    }
+    if (rank == H) lo = x;
+    if (rank == d - H - 1) hi = x;
+  }
+  lower = fminf(lo, own);
+  upper = fmaxf(hi, own);
+  float sum = 0.f;
+  for (int k = 0; k < d; ++k) sum += __builtin_amdgcn_fmed3f(tile[(nb[k] << log2tc) + c], lower, upper);
+  return sum / (float)d;
+}
+
 __global__ __launch_bounds__(256) void k_consensus_params_generic(const float* __restrict__ msg,
                                                                   float* __restrict__ theta,
                                                                   const int* __restrict__ nbr,
@@ -444,26 +466,123 @@ __global__ __launch_bounds__(256) void k_consensus_params_generic(const float* _
   const bool col_ok = (c0 + c) < P_hid;
   for (int i = threadIdx.x >> log2tc; i < N; i += rows_per_pass) {
     if (!coop[i]) continue;
-    const int* nb = nbr + i * d;
-    const float own = tile[(nb[0] << log2tc) + c];
-    float lo = own, hi = own;
-    for (int k = 0; k < d; ++k) {
-      const float x = tile[(nb[k] << log2tc) + c];
-      int rank = 0;
-      for (int m = 0; m < d; ++m) {
-        const float y = tile[(nb[m] << log2tc) + c];
-        rank += (y < x || (y == x && m < k)) ? 1 : 0;
-      }
-      if (rank == H) lo = x;
-      if (rank == d - H - 1) hi = x;
-    }
-    const float lower = fminf(lo, own), upper = fmaxf(hi, own);
-    float sum = 0.f;
-    for (int k = 0; k < d; ++k) sum += __builtin_amdgcn_fmed3f(tile[(nb[k] << log2tc) + c], lower, upper);
+    float lower, upper;
+    const float out = aggregate_rank_count(tile, nbr + i * d, log2tc, c, d, H, lower, upper);
     if (col_ok) {
       const size_t o = ((size_t)s * N + i) * ldp + c0 + c;
-      theta[o] = sum / (float)d;
+      theta[o] = out;
       if (lo_dbg) { lo_dbg[o] = lower; hi_dbg[o] = upper; }
+    }
+  }
+}
+
+// ---- irregular graphs: every (d, H) class of the cooperative agents in ONE launch ----------------------------------------
+// The graph arrives as CSR (nbr_off[N+1], nbr_idx[nnz]; nbr_idx[nbr_off[i]] == i) and the cooperative agents sorted by their
+// (d, H) class (order[]; the class table {d, H, first, count} rides in the kernel arguments).  Same persistent tile walk and
+// TileStager as k_consensus_params: the [N][TC] message tile is staged ONCE per (seed, column tile) -- one launch of
+// k_consensus_params per class would read the whole message matrix once per class, and K1 is HBM-bound at small d.  The workgroup
+// then walks the classes; (d, H) of a class is uniform, a scalar branch picks the generated SelNet<D, H> (aggregate_regs: the
+// per-agent code of k_consensus_params, so an agent's result has the bits rcmarl_consensus_params gives on a regular graph of its
+// class) or the rank counting of k_consensus_params_generic.
+// Code size: the switch instantiates each network once (d <= RC_RAGGED_MAX_NET_D; the few wider generated networks would
+// set the register budget of the whole kernel and take the rank-counting branch here).
+constexpr int RC_RAGGED_MAX_CLASSES = 32;   // classes per launch (the entry point issues further launches beyond)
+constexpr int RC_RAGGED_MAX_NET_D = 20;
+struct RaggedClasses {
+  int n;
+  int d[RC_RAGGED_MAX_CLASSES], H[RC_RAGGED_MAX_CLASSES], first[RC_RAGGED_MAX_CLASSES], count[RC_RAGGED_MAX_CLASSES];
+};
+
+template <int D, int H>
+__device__ __forceinline__ void ragged_class(const float* tile, float* __restrict__ theta, const int* __restrict__ nbr_off,
+                                             const int* __restrict__ nbr_idx, const int* __restrict__ order, int first,
+                                             int count, int N, int ldp, int log2tc, int s, int c0, int c, bool col_ok,
+                                             float* __restrict__ lo_dbg, float* __restrict__ hi_dbg) {
+  auto load_vals = [&](const int i, float (&v)[D]) {
+    const int* nb = nbr_idx + nbr_off[i];
+#pragma unroll
+    for (int k = 0; k < D; ++k) v[k] = tile[(nb[k] << log2tc) + c];
+  };
+  auto finish = [&](const int i, const float (&v)[D]) {
+    float lower, upper;
+    const float out = aggregate_regs<D, H>(v, lower, upper, lo_dbg != nullptr);
+    if (col_ok) {
+      const size_t o = ((size_t)s * N + i) * ldp + c0 + c;
+      theta[o] = out;
+      if (lo_dbg) { lo_dbg[o] = lower; hi_dbg[o] = upper; }
+    }
+  };
+  if (log2tc == 6) {
+    // one wavefront = one agent (an SGPR index: the neighbour list comes through the scalar cache); two agents per trip for ILP
+    int j = threadIdx.x >> 6;
+    for (; j + 4 < count; j += 8) {
+      const int ia = __builtin_amdgcn_readfirstlane(order[first + j]), ib = __builtin_amdgcn_readfirstlane(order[first + j + 4]);
+      float va[D], vb[D];
+      load_vals(ia, va);
+      load_vals(ib, vb);
+      finish(ia, va);
+      finish(ib, vb);
+    }
+    for (; j < count; j += 4) {
+      const int ia = __builtin_amdgcn_readfirstlane(order[first + j]);
+      float va[D];
+      load_vals(ia, va);
+      finish(ia, va);
+    }
+  } else {
+    for (int j = threadIdx.x >> log2tc; j < count; j += 256 >> log2tc) {
+      const int i = order[first + j];
+      float va[D];
+      load_vals(i, va);
+      finish(i, va);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_consensus_params_ragged(const float* __restrict__ msg, float* __restrict__ theta,
+                                                                 const int* __restrict__ nbr_off,
+                                                                 const int* __restrict__ nbr_idx,
+                                                                 const int* __restrict__ order, const RaggedClasses cls, int N,
+                                                                 int ldp, int P_hid, int log2tc, int tiles_per_seed,
+                                                                 int total_tiles, float* __restrict__ lo_dbg,
+                                                                 float* __restrict__ hi_dbg) {
+  RCMARL_DYN_SMEM(float, tile);
+  const int TC = 1 << log2tc;
+  const TileStager st{msg, N, ldp, log2tc, tiles_per_seed};
+  float pf[4 * PF];
+  int t = blockIdx.x;
+  if (t < total_tiles) st.fetch(t, pf);
+  const int c = threadIdx.x & (TC - 1);
+  for (; t < total_tiles; t += gridDim.x) {
+    __syncthreads();                       // every wave is done with the previous tile image
+    st.commit(pf, tile);
+    __syncthreads();
+    if (t + (int)gridDim.x < total_tiles) st.fetch(t + gridDim.x, pf);   // in flight during the aggregation below
+    const int s = t / tiles_per_seed, c0 = (t - s * tiles_per_seed) << log2tc;
+    const bool col_ok = (c0 + c) < P_hid;
+    for (int q = 0; q < cls.n; ++q) {
+      const int d = cls.d[q], H = cls.H[q], first = cls.first[q], count = cls.count[q];
+      switch (d <= RC_RAGGED_MAX_NET_D ? d * 64 + H : -1) {
+#define RC_RCASE(DD, HH)                                                                                                     \
+        case (DD <= RC_RAGGED_MAX_NET_D ? DD * 64 + HH : -2 - (DD * 64 + HH)):                                               \
+          if constexpr (DD <= RC_RAGGED_MAX_NET_D)                                                                           \
+            ragged_class<DD, HH>(tile, theta, nbr_off, nbr_idx, order, first, count, N, ldp, log2tc, s, c0, c, col_ok,       \
+                                 lo_dbg, hi_dbg);                                                                            \
+          break;
+        RCMARL_SELNET_COMBOS(RC_RCASE)
+#undef RC_RCASE
+        default:
+          for (int j = threadIdx.x >> log2tc; j < count; j += 256 >> log2tc) {
+            const int i = order[first + j];
+            float lower, upper;
+            const float out = aggregate_rank_count(tile, nbr_idx + nbr_off[i], log2tc, c, d, H, lower, upper);
+            if (col_ok) {
+              const size_t o = ((size_t)s * N + i) * ldp + c0 + c;
+              theta[o] = out;
+              if (lo_dbg) { lo_dbg[o] = lower; hi_dbg[o] = upper; }
+            }
+          }
+      }
     }
   }
 }
@@ -602,4 +721,48 @@ RCMARL_EXPORT int rcmarl_consensus_params_circulant(const float* msg, float* the
 #undef RC_CIRC_CASE
 #undef RC_CIRC_LAUNCH
   return rc;
+}
+
+// Irregular graphs: all (d, H) classes of the cooperative agents in one launch (k_consensus_params_ragged above).  `classes` is
+// HOST memory, read during the call only.  More than RC_RAGGED_MAX_CLASSES classes: one launch per 32 of them.
+RCMARL_EXPORT int rcmarl_consensus_params_ragged(const float* msg, float* theta, const int* nbr_off, const int* nbr_idx,
+                                                 const int* order, const rcmarl_ragged_class* classes, int n_classes, int S,
+                                                 int N, int ldp, int P_hid, float* lo_dbg, float* hi_dbg, void* stream) {
+  if (!msg || !theta || !nbr_off || !nbr_idx || !order || !classes || n_classes <= 0 || S <= 0 || N <= 0 || (ldp & 63) ||
+      P_hid <= 0 || P_hid > ldp || (!!lo_dbg != !!hi_dbg))
+    return RCMARL_ERR_ARG;
+  for (int q = 0; q < n_classes; ++q) {
+    const rcmarl_ragged_class& k = classes[q];
+    if (k.d <= 0 || k.d > N || k.H < 0 || k.d < 2 * k.H + 1 || k.first < 0 || k.count <= 0 || k.first > N - k.count)
+      return RCMARL_ERR_ARG;
+  }
+  // widest column tile whose [N][TC] fp32 image fits 64 KiB of LDS, as rcmarl_consensus_params
+  int log2tc = 6;
+  while (log2tc > 2 && ((size_t)N << log2tc) * sizeof(float) > 64 * 1024) --log2tc;
+  if (((size_t)N << log2tc) * sizeof(float) > 64 * 1024) return RCMARL_ERR_UNSUPPORTED;
+  const int TC = 1 << log2tc;
+  const size_t smem = ((size_t)N << log2tc) * sizeof(float);
+  const int tiles_per_seed = rc_ceil_div(P_hid, TC), total_tiles = tiles_per_seed * S;
+  // resident workgroups only (the tile walk is persistent): the kernel's 224 VGPRs leave 2 wavefronts per SIMD = 2 workgroups of 256
+  // threads per CU, whatever the LDS would allow
+  int wg_per_cu = (int)((160 * 1024) / (smem + 512));
+  if (wg_per_cu > 2) wg_per_cu = 2;
+  if (wg_per_cu < 1) wg_per_cu = 1;
+  int nwg = rc_persistent_grid(256 * wg_per_cu);
+  if (nwg > total_tiles) nwg = total_tiles;
+  if (!k1_want_lds(k_consensus_params_ragged, smem)) return RCMARL_ERR_LAUNCH;
+  for (int q0 = 0; q0 < n_classes; q0 += RC_RAGGED_MAX_CLASSES) {
+    RaggedClasses cls;
+    cls.n = n_classes - q0 < RC_RAGGED_MAX_CLASSES ? n_classes - q0 : RC_RAGGED_MAX_CLASSES;
+    for (int q = 0; q < RC_RAGGED_MAX_CLASSES; ++q) {
+      const bool in = q < cls.n;
+      cls.d[q] = in ? classes[q0 + q].d : 0; cls.H[q] = in ? classes[q0 + q].H : 0;
+      cls.first[q] = in ? classes[q0 + q].first : 0; cls.count[q] = in ? classes[q0 + q].count : 0;
+    }
+    RCMARL_LAUNCH(k_consensus_params_ragged, dim3(nwg), dim3(256), smem, stream, msg, theta, nbr_off, nbr_idx, order, cls, N, ldp,
+                  P_hid, log2tc, tiles_per_seed, total_tiles, lo_dbg, hi_dbg);
+    const int rc = rcmarl_check_launch();
+    if (rc != RCMARL_OK) return rc;
+  }
+  return RCMARL_OK;
 }

@@ -780,6 +780,11 @@ __global__ __launch_bounds__(256) void k_mid_value(const float* __restrict__ a1t
 // K2+K3.  For cooperative agent i: phi = features_{theta_i}(x); V_k = phi . W3(msg[nbr[i][k]]) + b3;
 // agg = resilient aggregate over k; residual e = (agg - V_live)/(|phi|^2+1);
 // partial[chunk] = [sum_b e*phi (HID) | sum_b e]
+// The two optional parameters of the consensus-head kernels (irregular graphs, rcmarl_consensus_head_ragged): `agents` -- workgroup
+// column y works on agent agents[y] (null: on agent y); `row_off` -- the neighbour list of agent i starts at nbr[row_off[i]]
+// (null: at nbr[i * d]).
+__device__ __forceinline__ int head_agent(const int* __restrict__ agents) { return agents ? agents[blockIdx.y] : (int)blockIdx.y; }
+
 template <int HID, int D, int H>
 __device__ __forceinline__ float select_agg(const float (&v)[D]) {
   float lo, hi;
@@ -796,10 +801,12 @@ __global__ __launch_bounds__(256) void k_consensus_head(const float* __restrict_
                                                         const float* __restrict__ msg, const int* __restrict__ nbr,
                                                         const int* __restrict__ coop,
                                                         float* __restrict__ partials, float* __restrict__ agg_out,
-                                                        int N, int B, int in_dim, int ldp, int ldb, int nchunk) {
+                                                        int N, int B, int in_dim, int ldp, int ldb, int nchunk,
+                                                        const int* __restrict__ agents, const int* __restrict__ row_off) {
   __shared__ float red[4 * (HID + 1)];
-  const int s = blockIdx.z, i = blockIdx.y, chunk = blockIdx.x;
-  if (!coop[i]) return;                       // workgroup-uniform
+  const int s = blockIdx.z, i = head_agent(agents), chunk = blockIdx.x;
+  if (coop && !coop[i]) return;               // workgroup-uniform
+  const int* __restrict__ nb = nbr + (row_off ? row_off[i] : i * D);
   const int b = chunk * ROWS + threadIdx.x;
   const bool valid = b < B;
   const NetGeom g = make_geom(in_dim, HID, 1);
@@ -814,7 +821,7 @@ __global__ __launch_bounds__(256) void k_consensus_head(const float* __restrict_
   float v[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) {
-    const float* mh = msg + ((long)s * N + nbr[i * D + k]) * ldp;
+    const float* mh = msg + ((long)s * N + nb[k]) * ldp;
     v[k] = head1<HID>(mh + g.o_W3, mh[g.o_b3], phi);
   }
   const float agg = select_agg<HID, D, H>(v);
@@ -859,15 +866,17 @@ __global__ __launch_bounds__(256, kK2mxWaves) void k_consensus_head_mx(const flo
                                                            const float* __restrict__ msg, const int* __restrict__ nbr,
                                                            const int* __restrict__ coop, float* __restrict__ partials,
                                                            float* __restrict__ agg_out, int N, int B, int in_dim, int ldp, int ldb,
-                                                           int nchunk, int cpw) {
+                                                           int nchunk, int cpw, const int* __restrict__ agents,
+                                                           const int* __restrict__ row_off) {
   constexpr int HID = 20, LU = 10, NH = D + 1, REC = HID + 2;
   static_assert(NH <= 32, "the heads of an agent are the 32 rows of one matrix-core operand");
   __shared__ __attribute__((aligned(16))) uint4 sWf[2 * 2 * 2 * 32];      // layer 2: [k-step][piece][k-group][row i] 16-byte A fragments
   __shared__ __attribute__((aligned(16))) uint4 sHf[2 * 2 * 2 * 32];      // heads:   [k-step][piece][k-group][head]
   __shared__ float red[4 * REC];                                          // per wavefront: sum_b e phi (20) | sum_b e (two halves)
   __shared__ int s_ovf;
-  const int s = blockIdx.z, i = blockIdx.y, chunk = blockIdx.x;
-  if (!coop[i]) return;                                                   // workgroup-uniform
+  const int s = blockIdx.z, i = head_agent(agents), chunk = blockIdx.x;
+  if (coop && !coop[i]) return;                                           // workgroup-uniform
+  const int* __restrict__ nb = nbr + (row_off ? row_off[i] : i * D);
   const int r = threadIdx.x, lane = r & 63, wave = __builtin_amdgcn_readfirstlane(r >> 6), l31 = lane & 31, half = lane >> 5;
   const NetGeom g = make_geom(in_dim, HID, 1);
   const float* __restrict__ th = theta + ((long)s * N + i) * ldp;
@@ -890,7 +899,7 @@ __global__ __launch_bounds__(256, kK2mxWaves) void k_consensus_head_mx(const flo
         if (ui >= 0 && uk >= 0) w = th[g.o_W2 + uk * HID + ui];
         if (ui >= 0 && bias) w = th[g.o_b2 + ui];
       } else if (ri < NH && (uk >= 0 || bias)) {
-        const float* src = ri < D ? msg + ((long)s * N + nbr[i * D + ri]) * ldp : th;
+        const float* src = ri < D ? msg + ((long)s * N + nb[ri]) * ldp : th;
         w = bias ? src[g.o_b3] : src[g.o_W3 + uk];
       }
       unsigned ph, pl;
@@ -1076,7 +1085,7 @@ __global__ __launch_bounds__(256, kK2mxWaves) void k_consensus_head_mx(const flo
       float v[D];
 #pragma unroll
       for (int k = 0; k < D; ++k) {
-        const float* mh = msg + ((long)s * N + nbr[i * D + k]) * ldp;
+        const float* mh = msg + ((long)s * N + nb[k]) * ldp;
         v[k] = head1<HID>(mh + g.o_W3, mh[g.o_b3], phi);
       }
       const float agg = select_agg<HID, D, H>(v);
@@ -1251,11 +1260,13 @@ template <int HID>
 __global__ __launch_bounds__(256) void k_consensus_head_generic(
     const float* __restrict__ a1t, const float* __restrict__ theta, const float* __restrict__ msg,
     const int* __restrict__ nbr, const int* __restrict__ coop, float* __restrict__ partials,
-    float* __restrict__ agg_out, int N, int B, int in_dim, int ldp, int ldb, int nchunk, int d, int H) {
+    float* __restrict__ agg_out, int N, int B, int in_dim, int ldp, int ldb, int nchunk, int d, int H,
+    const int* __restrict__ agents, const int* __restrict__ row_off) {
   __shared__ float red[4 * (HID + 1)];
   RCMARL_DYN_SMEM(float, est);                // [d][ROWS]
-  const int s = blockIdx.z, i = blockIdx.y, chunk = blockIdx.x;
-  if (!coop[i]) return;
+  const int s = blockIdx.z, i = head_agent(agents), chunk = blockIdx.x;
+  if (coop && !coop[i]) return;
+  const int* __restrict__ nb = nbr + (row_off ? row_off[i] : i * d);
   const int r = threadIdx.x, b = chunk * ROWS + r;
   const bool valid = b < B;
   const NetGeom g = make_geom(in_dim, HID, 1);
@@ -1268,7 +1279,7 @@ __global__ __launch_bounds__(256) void k_consensus_head_generic(
   for (int k = 0; k < HID; ++k) nrm = fmaf(phi[k], phi[k], nrm);
   nrm += 1.0f;
   for (int k = 0; k < d; ++k) {
-    const float* mh = msg + ((long)s * N + nbr[i * d + k]) * ldp;
+    const float* mh = msg + ((long)s * N + nb[k]) * ldp;
     est[k * ROWS + r] = head1<HID>(mh + g.o_W3, mh[g.o_b3], phi);
   }
   const float own = est[r];
@@ -1677,10 +1688,9 @@ RCMARL_EXPORT int rcmarl_mid_value_f32(const float* a1t, const float* theta, con
 template <int DD, int HH>
 static bool launch_consensus_head_mx(dim3 grid, dim3 block, void* stream, const float* a1t, const float* theta, const float* msg,
                                      const int* nbr, const int* coop, float* partials, float* agg_out, int N, int B, int in_dim,
-                                     int ldp, int ldb, int nchunk) {
+                                     int ldp, int ldb, int nchunk, long pairs, const int* agents, const int* row_off) {
   if constexpr (DD + 1 <= 32) {
     // chunks per workgroup: the whole agent when there are enough (seed, agent) pairs to fill the GPU, else fewer
-    const long pairs = (long)grid.y * grid.z;
     int wgs = pairs >= 2048 ? 2 : (pairs >= 512 ? 4 : nchunk);
     if (wgs * 32 < nchunk) wgs = (nchunk + 31) / 32;                      // (a wavefront keeps one bit per chunk)
     int cpw = (nchunk + wgs - 1) / wgs;
@@ -1688,21 +1698,22 @@ static bool launch_consensus_head_mx(dim3 grid, dim3 block, void* stream, const 
     if (ce && atoi(ce) >= 1 && atoi(ce) <= 32) cpw = atoi(ce);
     grid.x = (unsigned)((nchunk + cpw - 1) / cpw);
     RCMARL_LAUNCH((k_consensus_head_mx<DD, HH>), grid, block, 0, stream, a1t, theta, msg, nbr, coop, partials, agg_out, N, B, in_dim,
-                  ldp, ldb, nchunk, cpw);
+                  ldp, ldb, nchunk, cpw, agents, row_off);
     return true;
   } else {
     return false;
   }
 }
 
-RCMARL_EXPORT int rcmarl_consensus_head(const float* a1t, const float* theta, const float* msg, const int* nbr,
-                                        const int* coop, float* partials, float* agg_out, int S, int N,
-                                        int B, int in_dim, int hid, int ldp, int ldb, int d, int H, void* stream) {
-  if (bad_mid(a1t, theta, S, N, B, in_dim, hid, ldp, ldb) || !msg || !nbr || !coop || !partials || d <= 0 || H < 0 ||
-      d < 2 * H + 1)
-    return RCMARL_ERR_ARG;
+// One launch of the consensus head for n_y agents: `agents` (null: agents 0 .. n_y - 1, n_y == N), neighbour lists of d entries at
+// nbr + row_off[i] (null: nbr + i * d).  Kernel and chunking depend on (hid, d, H, S * N) only: a class of an irregular graph runs
+// what a regular graph of that (d, H) and the same S x N runs.
+static int consensus_head_launch(const float* a1t, const float* theta, const float* msg, const int* nbr, const int* coop,
+                                 const int* agents, const int* row_off, int n_y, float* partials, float* agg_out, int S, int N,
+                                 int B, int in_dim, int hid, int ldp, int ldb, int d, int H, void* stream) {
   const int nchunk = rc_ceil_div(B, ROWS);
-  const dim3 grid(nchunk, N, S), block(ROWS);
+  const dim3 grid(nchunk, n_y, S), block(ROWS);
+  const long pairs = (long)N * S;
   bool done = false;
   // RCMARL_K2_MX (default 1): layer 2 and the d + 1 heads on the f16 matrix core (k_consensus_head_mx: 20 units, d + 1 <= 32 heads, a
   // generated selection network); 0: everything on the vector ALUs (k_consensus_head)
@@ -1712,10 +1723,10 @@ RCMARL_EXPORT int rcmarl_consensus_head(const float* a1t, const float* theta, co
 #define RC_CASE(DD, HH)                                                                                          \
   if (!done && d == DD && H == HH) {                                                                             \
     if (mx) done = launch_consensus_head_mx<DD, HH>(grid, block, stream, a1t, theta, msg, nbr, coop, partials, agg_out, N, B, in_dim,  \
-                                                    ldp, ldb, nchunk);                                           \
+                                                    ldp, ldb, nchunk, pairs, agents, row_off);                   \
     if (!done) {                                                                                                 \
       RC_HID_SWITCH(hid, RCMARL_LAUNCH((k_consensus_head<HID_, DD, HH>), grid, block, 0, stream, a1t, theta, msg,  \
-                                       nbr, coop, partials, agg_out, N, B, in_dim, ldp, ldb, nchunk));          \
+                                       nbr, coop, partials, agg_out, N, B, in_dim, ldp, ldb, nchunk, agents, row_off));  \
       done = true;                                                                                               \
     }                                                                                                            \
   }
@@ -1725,9 +1736,44 @@ RCMARL_EXPORT int rcmarl_consensus_head(const float* a1t, const float* theta, co
     const size_t smem = (size_t)d * ROWS * sizeof(float);
     if (smem > 60 * 1024) return RCMARL_ERR_UNSUPPORTED;
     RC_HID_SWITCH(hid, RCMARL_LAUNCH((k_consensus_head_generic<HID_>), grid, block, smem, stream, a1t, theta, msg, nbr,
-                                     coop, partials, agg_out, N, B, in_dim, ldp, ldb, nchunk, d, H));
+                                     coop, partials, agg_out, N, B, in_dim, ldp, ldb, nchunk, d, H, agents, row_off));
   }
   return rcmarl_check_launch();
+}
+
+RCMARL_EXPORT int rcmarl_consensus_head(const float* a1t, const float* theta, const float* msg, const int* nbr,
+                                        const int* coop, float* partials, float* agg_out, int S, int N,
+                                        int B, int in_dim, int hid, int ldp, int ldb, int d, int H, void* stream) {
+  if (bad_mid(a1t, theta, S, N, B, in_dim, hid, ldp, ldb) || !msg || !nbr || !coop || !partials || d <= 0 || H < 0 ||
+      d < 2 * H + 1)
+    return RCMARL_ERR_ARG;
+  return consensus_head_launch(a1t, theta, msg, nbr, coop, nullptr, nullptr, N, partials, agg_out, S, N, B, in_dim, hid, ldp, ldb, d,
+                               H, stream);
+}
+
+// Irregular graphs (include/rcmarl.h): the work is per agent already -- one workgroup column per (seed, agent) -- so one launch per
+// (d, H) class costs no extra traffic; grid.y = the class's agent count, the kernels read their agent from order[first + y] and its
+// neighbour list at nbr_idx + nbr_off[agent].  `classes` is HOST memory.
+RCMARL_EXPORT int rcmarl_consensus_head_ragged(const float* a1t, const float* theta, const float* msg, const int* nbr_off,
+                                               const int* nbr_idx, const int* order, const rcmarl_ragged_class* classes,
+                                               int n_classes, float* partials, float* agg_out, int S, int N, int B, int in_dim,
+                                               int hid, int ldp, int ldb, void* stream) {
+  if (bad_mid(a1t, theta, S, N, B, in_dim, hid, ldp, ldb) || !msg || !nbr_off || !nbr_idx || !order || !classes || !partials ||
+      n_classes <= 0)
+    return RCMARL_ERR_ARG;
+  for (int q = 0; q < n_classes; ++q) {
+    const rcmarl_ragged_class& k = classes[q];
+    if (k.d <= 0 || k.d > N || k.H < 0 || k.d < 2 * k.H + 1 || k.first < 0 || k.count <= 0 || k.first > N - k.count)
+      return RCMARL_ERR_ARG;
+    if ((size_t)k.d * ROWS * sizeof(float) > 60 * 1024) return RCMARL_ERR_UNSUPPORTED;      // (before anything is launched)
+  }
+  for (int q = 0; q < n_classes; ++q) {
+    const rcmarl_ragged_class& k = classes[q];
+    const int rc = consensus_head_launch(a1t, theta, msg, nbr_idx, nullptr, order + k.first, nbr_off, k.count, partials, agg_out, S,
+                                         N, B, in_dim, hid, ldp, ldb, k.d, k.H, stream);
+    if (rc != RCMARL_OK) return rc;
+  }
+  return RCMARL_OK;
 }
 
 RCMARL_EXPORT int rcmarl_projection_residual(const float* a1t, const float* theta, const float* agg, const int* coop,

@@ -37,6 +37,15 @@ static_assert(sizeof(rcmarl_mb_job) == 80 && offsetof(rcmarl_mb_job, x_seed_stri
               offsetof(rcmarl_mb_job, loss_out) == 64 && offsetof(rcmarl_mb_job, ovf_flags) == 72,
               "rcmarl_mb_job: the layout include/rcmarl.h and capi.MbJob declare");
 
+// one (d, H) class of rcmarl_consensus_params_ragged / rcmarl_consensus_head_ragged.  Declared here, in include/rcmarl.h and as
+// capi.RaggedClass (ctypes); rcmarl_ragged_class_layout() (abi.hip) hands the numbers to tests/test_ragged_capi.py.
+typedef struct rcmarl_ragged_class {
+  int d, H;                                /* in-neighbourhood size (own value included) and trim parameter of the class */
+  int first, count;                        /* its agents: order[first .. first + count) */
+} rcmarl_ragged_class;
+static_assert(sizeof(rcmarl_ragged_class) == 16 && offsetof(rcmarl_ragged_class, H) == 4 && offsetof(rcmarl_ragged_class, first) == 8 &&
+              offsetof(rcmarl_ragged_class, count) == 12, "rcmarl_ragged_class: the layout include/rcmarl.h and capi.RaggedClass declare");
+
 #ifdef RCMARL_EMU
 #define RCMARL_LAUNCH(kernel, grid, block, smem, stream, ...) \
   hipemu::launch((grid), (block), (smem), [=]() { kernel(__VA_ARGS__); })

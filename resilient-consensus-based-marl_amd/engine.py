@@ -55,7 +55,12 @@ def unflatten_params(vec, in_dim, out_dim, hid=HID):
 
 class EngineConfig:
     """Same keys as the reference's ``args`` dict (main.py:26-44) plus the
-    grid size, seed count and RNG mode."""
+    grid size, seed count and RNG mode.
+
+    in_nodes: N lists of any lengths d_i >= 1 with in_nodes[i][0] == i (training/train_agents.py:129-130 indexes a plain list of
+    lists); H: an int or a sequence of N ints (RPBCAC_agent(..., H=...) is per agent).  Cooperative agents need d_i >= 2 H_i + 1;
+    rows of the others are never used for consensus.  `degrees`, `H_per_agent` hold both per agent; `regular` says that all
+    degrees and all H are equal -- then `d` and `H` are those values and the engine takes the uniform-graph kernels."""
 
     def __init__(self, n_agents, agent_label, in_nodes, H=0, gamma=0.9, slow_lr=0.002, fast_lr=0.01, n_actions=5,
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
@@ -63,7 +68,7 @@ class EngineConfig:
                  local_fit_steps=5, lattice="auto", critic_hid=HID):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
-        self.H, self.gamma, self.slow_lr, self.fast_lr = int(H), float(gamma), float(slow_lr), float(fast_lr)
+        self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
         self.n_actions, self.n_states = int(n_actions), int(n_states)
         self.max_ep_len, self.n_ep_fixed, self.n_epochs = int(max_ep_len), int(n_ep_fixed), int(n_epochs)
         self.buffer_size, self.common_reward = int(buffer_size), bool(common_reward)
@@ -75,14 +80,24 @@ class EngineConfig:
         # the critic to 512 units): any other width runs the dense-GEMM path of csrc/wide_kernels.hip
         self.critic_hid = int(critic_hid)
         assert len(self.agent_label) == self.n_agents and len(self.in_nodes) == self.n_agents
-        d = len(self.in_nodes[0])
+        if np.ndim(H) == 0:
+            self.H_per_agent = [int(H)] * self.n_agents
+        else:
+            self.H_per_agent = [int(h) for h in H]
+            if len(self.H_per_agent) != self.n_agents:
+                raise ValueError("H must be an int or one int per agent (got %d for %d agents)" % (len(self.H_per_agent), self.n_agents))
+        self.degrees = [len(row) for row in self.in_nodes]
         for i, row in enumerate(self.in_nodes):
-            if len(row) != d:
-                raise ValueError("all in-neighbourhoods must have the same size d (got %d and %d)" % (d, len(row)))
-            if row[0] != i:
+            if not row or row[0] != i:
                 raise ValueError("in_nodes[i][0] must be i (own value first, agents/resilient_CAC_agents.py:49)")
-        if d < 2 * self.H + 1:
-            raise ValueError("need d >= 2H+1")
+            if any(j < 0 or j >= self.n_agents for j in row):
+                raise ValueError("in_nodes[%d] names an agent outside 0..%d" % (i, self.n_agents - 1))
+            if self.agent_label[i] == COOP and (self.H_per_agent[i] < 0 or len(row) < 2 * self.H_per_agent[i] + 1):
+                raise ValueError("need d >= 2H+1 (agent %d: d = %d, H = %d)" % (i, len(row), self.H_per_agent[i]))
+        self.regular = len(set(self.degrees)) == 1 and len(set(self.H_per_agent)) == 1
+        # regular graph: THE trim parameter; otherwise the largest one of a cooperative agent (a summary, not used for consensus)
+        self.H = self.H_per_agent[0] if self.regular else max([h for h, l in zip(self.H_per_agent, self.agent_label) if l == COOP],
+                                                               default=max(self.H_per_agent))
         if self.n_states != 2 or self.n_actions != 5:
             raise ValueError("the grid-world has 2 state dims and 5 actions per agent")
         if rng_mode not in ("device", "numpy"):
@@ -92,10 +107,28 @@ class EngineConfig:
                 raise ValueError("unknown agent label %r" % lab)
         if self.critic_hid < 1:
             raise ValueError("critic_hid must be positive")
+        if not self.regular and self.critic_hid != HID:
+            raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit critic: the wide head's gather / "
+                             "GEMM / select chain is sized by one d (critic_hid = %d)" % self.critic_hid)
 
     @property
     def d(self):
-        return len(self.in_nodes[0])
+        """in-neighbourhood size (own value included) of a regular graph; the largest one of an irregular graph"""
+        return max(self.degrees)
+
+    def consensus_classes(self):
+        """The (d, H) classes of the cooperative agents -> (order, classes): the cooperative agents sorted by class (agent index
+        within a class) and one (d, H, first, count) per class, ascending in (d, H)."""
+        coop = [i for i, l in enumerate(self.agent_label) if l == COOP]
+        order = sorted(coop, key=lambda i: (self.degrees[i], self.H_per_agent[i], i))
+        classes = []
+        for pos, i in enumerate(order):
+            key = (self.degrees[i], self.H_per_agent[i])
+            if classes and tuple(classes[-1][:2]) == key:
+                classes[-1][3] += 1
+            else:
+                classes.append([key[0], key[1], pos, 1])
+        return order, [tuple(k) for k in classes]
 
 
 class RPBCACEngine:
@@ -167,10 +200,22 @@ class RPBCACEngine:
         self.seeds = seeds
         self.seeds_dev = torch.tensor(np.asarray(seeds, dtype=np.uint64).view(np.int64), dtype=torch.int64, device=self.dev)
         # graph / roles
-        self.nbr = torch.tensor(np.asarray(c.in_nodes, dtype=np.int32), **i32)
+        if c.regular:
+            self.nbr = torch.tensor(np.asarray(c.in_nodes, dtype=np.int32), **i32)
+        else:
+            # irregular graph / per-agent H: the graph as CSR, the cooperative agents sorted by their (d, H) class and the class
+            # table (host memory) of rcmarl_consensus_params_ragged / rcmarl_consensus_head_ragged, derived once
+            self.nbr = None
+            off = np.concatenate([[0], np.cumsum(c.degrees)]).astype(np.int32)
+            self.nbr_off = torch.tensor(off, **i32)
+            self.nbr_idx = torch.tensor(np.asarray([j for row in c.in_nodes for j in row], dtype=np.int32), **i32)
+            order, classes = c.consensus_classes()
+            self.order = torch.tensor(np.asarray(order, dtype=np.int32), **i32)
+            self.classes = classes                                   # [(d, H, first, count)]
+            self.class_table = (capi.RaggedClass * max(1, len(classes)))(*[capi.RaggedClass(*k) for k in classes])
         # circulant in-graph (the reference's own pattern, main.py:28) with d = 2H+2: K1 shares one selection
         # network among consecutive agents (rcmarl_consensus_params_circulant; RCMARL_K1_CIRC=0 disables)
-        circ = all(row == [(i + k) % N for k in range(c.d)] for i, row in enumerate(c.in_nodes))
+        circ = c.regular and all(row == [(i + k) % N for k in range(c.d)] for i, row in enumerate(c.in_nodes))
         self.k1_circulant = bool(circ and os.environ.get("RCMARL_K1_CIRC", "1") not in ("0", "false")
                                  and lib.rcmarl_consensus_params_circulant_supported(N, c.d, c.H))
         coop = np.array([1 if l == COOP else 0 for l in c.agent_label], dtype=np.int32)
@@ -476,6 +521,9 @@ class RPBCACEngine:
         force: shard even at world size 1, so that EVERY collective of the sharded instance runs through the communicator
         (the one-rank RCCL run on a single-GPU box: tests/test_rccl_one_rank_gpu.py, `bench.py --workload cfg5_shard`)."""
         from .parallel import ShardedConsensus, TorchComm, agent_range
+        if not self.cfg.regular:
+            raise ValueError("agent sharding needs a regular communication graph with one H: the column-sharded consensus "
+                             "(parallel.ShardedConsensus) takes one (d, H)")
         if comm is None and world is None:
             comm = TorchComm(group)
         if comm is not None:
@@ -812,7 +860,7 @@ class RPBCACEngine:
             sd[k] = getattr(self, k).detach().cpu()
         if hasattr(self, "adv"):
             sd["adv"] = self.adv.state_dict()
-        sd["shape"] = {"H": c.H, "critic_hid": c.critic_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
+        sd["shape"] = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
                        "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
         if self.np_rngs is not None:          # plain tensors / numbers only, so the file loads with weights_only=True
             sd["np_rngs"] = []
@@ -828,10 +876,12 @@ class RPBCACEngine:
             raise ValueError("checkpoint does not match this engine (format/S/N/agent labels)")
         if [list(map(int, r)) for r in sd["in_nodes"]] != c.in_nodes:
             raise ValueError("checkpoint was written for a different communication graph")
-        mine = {"H": c.H, "critic_hid": c.critic_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
+        mine = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
                 "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
         theirs = sd.get("shape", mine)
         diff = {k: (theirs.get(k), v) for k, v in mine.items() if theirs.get(k) != v}
+        if "H" in diff and self._H_list(theirs.get("H")) == c.H_per_agent:      # the same per-agent H, written the other way
+            del diff["H"]
         if diff:
             raise ValueError("checkpoint does not match this engine: %r (checkpoint, engine)" % diff)
         for k, v in sd["theta"].items():
@@ -863,6 +913,16 @@ class RPBCACEngine:
         self.a1_cached["critic"] = self.a1_cached["tr"] = self.a2_cached = False
         self.lat_active = False
         self.rows_episode_aligned = bool(sd.get("rows_episode_aligned", False))
+
+    def _ckpt_H(self):
+        """H as a checkpoint stores it: the scalar when uniform (the form of checkpoints written before per-agent H), else the list"""
+        hs = self.cfg.H_per_agent
+        return hs[0] if len(set(hs)) == 1 else list(hs)
+
+    def _H_list(self, h):
+        if h is None:
+            return None
+        return [int(h)] * self.N if np.ndim(h) == 0 else [int(x) for x in h]
 
     def save_checkpoint(self, path):
         torch.save(self.state_dict(), path)
@@ -1116,7 +1176,12 @@ class RPBCACEngine:
             sc.consensus()
             sc.gather(self.theta[net])
             return
-        if self.k1_circulant:
+        if not c.regular:
+            if self.classes:
+                L.rcmarl_consensus_params_ragged(self.msg[net].data_ptr(), self.theta[net].data_ptr(), self.nbr_off.data_ptr(),
+                                                 self.nbr_idx.data_ptr(), self.order.data_ptr(), self.class_table, len(self.classes),
+                                                 self.S, self.N, self.ldp[net], g_hid, None, None, self.stream)
+        elif self.k1_circulant:
             L.rcmarl_consensus_params_circulant(self.msg[net].data_ptr(), self.theta[net].data_ptr(), self.coop.data_ptr(),
                                                 self.S, self.N, self.ldp[net], g_hid, c.d, c.H, None, None, self.stream)
         else:
@@ -1255,9 +1320,16 @@ class RPBCACEngine:
         self._k1(net, self.P[net] - (HID * 1 + 1))
         a1 = self.a1net[net]
         self._layer1(xkey, self.theta[net], net, B, buf=a1)
-        L.rcmarl_consensus_head(a1.data_ptr(), self.theta[net].data_ptr(), msg_all.data_ptr(),
-                                self.nbr.data_ptr(), self.coop.data_ptr(), self.partials.data_ptr(), None, S, N, B,
-                                self.in_dim[net], HID, self.ldp[net], self.ldb, c.d, c.H, self.stream)
+        if not c.regular:
+            if self.classes:
+                L.rcmarl_consensus_head_ragged(a1.data_ptr(), self.theta[net].data_ptr(), msg_all.data_ptr(), self.nbr_off.data_ptr(),
+                                               self.nbr_idx.data_ptr(), self.order.data_ptr(), self.class_table, len(self.classes),
+                                               self.partials.data_ptr(), None, S, N, B, self.in_dim[net], HID, self.ldp[net],
+                                               self.ldb, self.stream)
+        else:
+            L.rcmarl_consensus_head(a1.data_ptr(), self.theta[net].data_ptr(), msg_all.data_ptr(),
+                                    self.nbr.data_ptr(), self.coop.data_ptr(), self.partials.data_ptr(), None, S, N, B,
+                                    self.in_dim[net], HID, self.ldp[net], self.ldb, c.d, c.H, self.stream)
         self.a1_cached[net] = self.reuse_activations       # hidden layers of the live net do not move until the next K1
         L.rcmarl_head_apply(self.partials.data_ptr(), self.theta[net].data_ptr(), self.coop.data_ptr(), S, N, B,
                             self.in_dim[net], HID, self.ldp[net], self.stream)
@@ -1345,7 +1417,7 @@ class RPBCACEngine:
     def _epoch(self, B, epoch, t0):
         if epoch == 0 or not self._graph_wanted() or not (self.a1_cached["critic"] and self.a1_cached["tr"]):
             return self._epoch_body(B, t0)
-        key = (B, self.lat_active, bool(self.td_shortcut), bool(self.rows_episode_aligned), bool(self.k1_circulant),
+        key = (B, self.lat_active, bool(self.td_shortcut), bool(self.rows_episode_aligned), bool(self.k1_circulant), bool(self.cfg.regular),
                bool(self.reuse_activations), self.cap, self.lib.rcmarl_lattice_f16_mode(), os.environ.get("RCMARL_LAT_W8"),
                os.environ.get("RCMARL_MIDFIT"),
                # the adversaries' launch form is re-read every epoch (AdversaryPath._multi_ok, phase1): a captured epoch belongs to one form

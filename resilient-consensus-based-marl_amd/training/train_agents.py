@@ -34,7 +34,14 @@ def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
     if widths["actor"] != {20} or widths["TR"] != {20} or len(widths["critic"]) != 1:
         raise ValueError("unsupported hidden widths %r: actor and team-reward net must have 20 hidden units and all critics "
                          "the same width" % widths)
-    cfg = EngineConfig(n_agents, labels, args['in_nodes'], critic_hid=widths["critic"].pop(), H=args['H'], gamma=args['gamma'],
+    # H is per agent (RPBCAC_agent(..., H=...)); the adversaries' classes carry none and never aggregate.  args['H'] may itself be
+    # one int or one per agent (main.py --H)
+    H_args = args['H'] if np.ndim(args['H']) else [args['H']] * n_agents
+    H = [int(getattr(ag, 'H', H_args[i])) for i, ag in enumerate(agents)]
+    H_coop = {h for h, lab in zip(H, labels) if lab == 'Cooperative'}
+    if len(H_coop) == 1:                       # one H among the cooperative agents: the uniform-H kernels
+        H = H_coop.pop()
+    cfg = EngineConfig(n_agents, labels, args['in_nodes'], critic_hid=widths["critic"].pop(), H=H, gamma=args['gamma'],
                        slow_lr=args['slow_lr'],
                        fast_lr=args['fast_lr'], n_actions=args['n_actions'], n_states=args['n_states'],
                        max_ep_len=args['max_ep_len'], n_ep_fixed=args['n_ep_fixed'], n_epochs=args['n_epochs'],
@@ -42,9 +49,6 @@ def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
                        ncol=env.ncol, n_seeds=1, rng_mode=args.get('rng_mode', 'numpy'),
                        scaling=bool(getattr(env, 'scaling', not np.isscalar(env.mean_state))),
                        randomize_state=env.randomize_state)
-    for ag in agents:
-        if getattr(ag, 'H', cfg.H) != cfg.H:
-            raise ValueError("all cooperative agents must use H = args['H']")
     lib, device = engine_hook if engine_hook is not None else (None, "cuda")
     eng = RPBCACEngine(cfg, seeds=[int(args.get('random_seed', 0))], device=device, lib=lib)
     # ---- agents -> stacked parameter matrices

@@ -3,6 +3,7 @@
 
     python tools/kbench.py gemm      # layer-1 GEMMs (variant via RCMARL_GEMM=0|1|2)
     python tools/kbench.py k1        # consensus_params at (d,H) = (4,1), (10,4), (18,8)
+    python tools/kbench.py k1_ragged # consensus_params_ragged on a degree mix against one masked uniform launch per class
     python tools/kbench.py mid       # mid_fit / consensus_head / mid_value
 """
 import os
@@ -87,6 +88,58 @@ def k1(L, S=16, N=256):
                 t = timeit(lambda: L.rcmarl_consensus_params_circulant(msg.data_ptr(), theta.data_ptr(), coop.data_ptr(), S, N, ldp,
                                                                        P_hid, d, H, None, None, st), iters=20)
                 print("   circulant kernel     %7.1f us  %7.1f GB/s (%.1f%% of 8 TB/s)" % (t, byts / t / 1e3, byts / t / 1e3 / 80))
+
+
+def k1_ragged(L, S=16, N=256, repeats=5):
+    """rcmarl_consensus_params_ragged against its alternative on a degree mix: half the agents (4, 1), a quarter (10, 4), a quarter
+    (18, 8); the team-reward net's P_hid.  (a) one ragged launch; (b) three masked rcmarl_consensus_params launches, same process,
+    same buffers -- the yardstick.  Then the all-(4, 1) regular graph through both entries: what the class walk costs against the
+    uniform kernel.  `repeats` timings of 20 launches each (HIP events); prints them and one JSON line (median, min, max in us)."""
+    import json
+    st = torch.cuda.current_stream().cuda_stream
+    in_dim = 3 * N
+    P = in_dim * HID + HID + HID * HID + HID + HID + 1
+    P_hid, ldp = P - 21, pad64(P)
+    msg = torch.randn(S, N, ldp, device="cuda")
+    theta = torch.zeros(S, N, ldp, device="cuda")
+    i32 = dict(dtype=torch.int32, device="cuda")
+
+    def setup(mix):
+        """mix: [(d, H, count)] over consecutive agents -> (ragged call, [masked uniform calls])"""
+        deg, Hs = [], []
+        for d, H, cnt in mix:
+            deg += [d] * cnt
+            Hs += [H] * cnt
+        rows = [[(i + k) % N for k in range(deg[i])] for i in range(N)]
+        off = torch.tensor(np.concatenate([[0], np.cumsum(deg)]).astype(np.int32), **i32)
+        idx = torch.tensor(np.asarray([j for r in rows for j in r], np.int32), **i32)
+        order = torch.arange(N, **i32)
+        table = (capi.RaggedClass * len(mix))()
+        first, uni = 0, []
+        for q, (d, H, cnt) in enumerate(mix):
+            table[q] = capi.RaggedClass(d, H, first, cnt)
+            nbr = torch.tensor([rows[i] if deg[i] == d else [i] * d for i in range(N)], **i32)
+            mask = torch.zeros(N, **i32)
+            mask[first:first + cnt] = 1
+            uni.append((nbr, mask, d, H))
+            first += cnt
+        keep = (off, idx, order, table, uni)
+        rag = lambda: L.rcmarl_consensus_params_ragged(msg.data_ptr(), theta.data_ptr(), off.data_ptr(), idx.data_ptr(), order.data_ptr(),
+                                                       table, len(mix), S, N, ldp, P_hid, None, None, st)
+
+        def masked():
+            for nbr, mask, d, H in uni:
+                L.rcmarl_consensus_params(msg.data_ptr(), theta.data_ptr(), nbr.data_ptr(), mask.data_ptr(), S, N, ldp, P_hid, d, H, None,
+                                          None, st)
+        return rag, masked, keep
+    out = {"S": S, "N": N, "P_hid": P_hid, "repeats": repeats, "launches_per_repeat": 20}
+    for name, mix in (("mix_4_1_10_4_18_8", [(4, 1, N // 2), (10, 4, N // 4), (18, 8, N - N // 2 - N // 4)]), ("regular_4_1", [(4, 1, N)])):
+        rag, masked, keep = setup(mix)
+        for label, fn in (("ragged", rag), ("uniform_per_class", masked)):
+            ts = sorted(timeit(fn, iters=20) for _ in range(repeats))
+            out["%s/%s" % (name, label)] = {"median_us": ts[len(ts) // 2], "min_us": ts[0], "max_us": ts[-1]}
+            print("K1 %-18s %-18s median %7.1f us  (min %7.1f, max %7.1f)" % (name, label, ts[len(ts) // 2], ts[0], ts[-1]))
+    print(json.dumps({"kbench": "k1_ragged", **out}))
 
 
 def k1_cfg5(L):
@@ -484,4 +537,4 @@ if __name__ == "__main__":
     L = capi.CLib(os.environ["RCMARL_KBENCH_LIB"]) if os.environ.get("RCMARL_KBENCH_LIB") else capi.load()     # (variant builds)
     what = sys.argv[1] if len(sys.argv) > 1 else "gemm"
     print("== %s  RCMARL_GEMM=%s RCMARL_K1=%s" % (what, os.environ.get("RCMARL_GEMM"), os.environ.get("RCMARL_K1")))
-    {"gemm": gemm, "k1": k1, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk}[what](L)
+    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk}[what](L)
