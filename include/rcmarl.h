@@ -336,6 +336,31 @@ int rcmarl_env_reset_episodes(const int* pos_in, const unsigned long long* seeds
                               const double* scale, int episode0, int* posT, float* xsT, double* retT, int S, int N,
                               int E, int EP, void* stream);
 
+/* Wide actors (hidden width != 20; actor.predict inside get_action, agents/resilient_CAC_agents.py:208-219, and the step that
+ * follows, training/train_agents.py:66-80).  rcmarl_policy_probs_wide / rcmarl_rollout_step_wide: the argument lists and results of
+ * rcmarl_policy_probs / rcmarl_rollout_step for ANY hid (one workgroup per (seed, agent), fp32 FMAs; hid up to 8188: two
+ * activation vectors in LDS).  rcmarl_rollout_step_episodes_wide: rcmarl_rollout_step_episodes on the matrix core
+ * (v_mfma_f32_32x32x16_f16, two-piece f16 operands, three piece products, fp32 fallback inside the launch when an operand leaves the
+ * f16 range; the exact operand form -- rcmarl_lattice_set_f16_mode(0) or rcmarl_wide_set_f16_mode(0) -- takes the fp32 MFMA); the two
+ * layers' activations stay in LDS / registers.  It serves the widths rcmarl_rollout_wide_supported(hid) reports (1: hid % 32 == 0
+ * and hid <= 512, the activations of 64 episodes within the LDS); others return RCMARL_ERR_UNSUPPORTED. */
+int rcmarl_policy_probs_wide(const float* xs, const float* theta, float* probs, int S, int N, int in_dim, int hid,
+                             int n_actions, int ldp, void* stream);
+int rcmarl_rollout_step_wide(const float* xs, const int* pos, const int* goal, const float* theta,
+                             const unsigned long long* seeds, int nrow, int ncol, const double* scale, float* rp_s,
+                             float* rp_ns, float* rp_sa, float* rp_a, float* rp_r, long cap, long row, int* pos_next,
+                             float* xs_next, double* ret, double gpow, int episode, int step, float mu, int S, int N,
+                             int hid, int n_actions, int ldp, int* act_out, void* stream);
+int rcmarl_rollout_wide_supported(int hid);
+/* probs[S][N][EP][5] (entries e < E written): the policy rcmarl_rollout_step_episodes_wide draws from, by the same kernel */
+int rcmarl_policy_probs_episodes_wide(const float* xsT, const float* theta, float* probs, int S, int N, int E, int EP, int hid,
+                                      int n_actions, int ldp, void* stream);
+int rcmarl_rollout_step_episodes_wide(const float* xsT, const int* posT, const int* goal, const float* theta,
+                                      const unsigned long long* seeds, int nrow, int ncol, const double* scale, float* rp_s,
+                                      float* rp_ns, float* rp_sa, float* rp_a, float* rp_r, long cap, long row0, int ep_len,
+                                      int* posT_next, float* xsT_next, double* retT, double gpow, int episode0, int step,
+                                      float mu, int S, int N, int E, int EP, int hid, int n_actions, int ldp, void* stream);
+
 /* ---- wide networks (any hidden width: BASELINE configs[4], the 512-unit critic) -- csrc/wide_kernels.hip ----
  * The reference builds its networks in main.py:59-82 with 20 hidden units; a wider model object handed to the same
  * agent API makes every layer a true dense GEMM per agent (f32 MFMA), the 1-unit head a column/row pass over the
@@ -395,6 +420,25 @@ int rcmarl_wide_consensus_head_nrm(const float* phi, const float* nparts, int n_
 /* W3 += grads[0..hid)/B, b3 += grads[hid]/B (cooperative agents) */
 int rcmarl_wide_head_apply(const float* grads, float* theta, const int* coop, int S, int N, int B, int in_dim, int hid,
                            int ldp, void* stream);
+
+/* Wide actor update (actor_update, agents/resilient_CAC_agents.py:86-101: one train_on_batch(s, a, sample_weight=td) Adam step).
+ * Forward: rcmarl_dense_forward twice.  rcmarl_wide_actor_head: logits, softmax, dz3[S][N*5][ldb] = w_b (p - onehot(a)) / B with
+ * Keras's sample-weight reduction as rcmarl_mid_actor computes it, loss parts; act_t / delta: [S][N][ldy].  Then
+ * rcmarl_dense_backward_data twice (J = 5, then J = hid) and rcmarl_dense_backward_adam three times: the weight-gradient GEMM
+ * of rcmarl_dense_backward_sgd whose epilogue is the Adam step on theta, adam_m, adam_v ([S][N][ldp] each; alpha = lr
+ * sqrt(1 - b2^t) / (1 - b1^t) from the caller, TF2 ResourceApplyAdam).  rcmarl_wide_actor_small_adam: b1, b2, b3 (row sums of
+ * dz1, dz2, dz3) and the loss.  The caller orders the launches so that every gradient is formed from pre-step weights. */
+int rcmarl_dense_backward_adam(const float* in, long in_seed_stride, long in_agent_stride, int in_row_major, int ld_in,
+                               const float* dz, float* theta, float* adam_m, float* adam_v, int w_off, const int* mask, int S,
+                               int N, int B, int K, int J, int ldp, int ldb, float alpha, float one_m_b1, float one_m_b2,
+                               float eps, void* stream);
+int rcmarl_wide_actor_head(const float* a2, const float* theta, const float* act_t, const float* delta, int ldy, float* dz3,
+                           float* losspart, int S, int N, int B, int in_dim, int hid, int n_actions, int ldp, int ldb,
+                           void* stream);
+int rcmarl_wide_actor_small_adam(const float* dz1, const float* dz2, const float* dz3, const float* losspart, float* theta,
+                                 float* adam_m, float* adam_v, const int* mask, float* loss_out, int S, int N, int B,
+                                 int in_dim, int hid, int n_actions, int ldp, int ldb, float alpha, float one_m_b1,
+                                 float one_m_b2, float eps, void* stream);
 
 
 /* ---- wide networks on PRE-SPLIT packed operands (ABI 4, round 6) -- csrc/dense_pk.hip ------------------------------------------

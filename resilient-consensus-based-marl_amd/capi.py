@@ -214,13 +214,36 @@ SIGNATURES = {
     # gw3part, q, gb1part, dz3, losspart, theta, mask, loss_out, S, N, B, in_dim, hid, ldp, ldb, lr, stream
     "rcmarl_pk_small_sgd": [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int,
                             c_int, c_float, c_stream],
+    # ---- wide actors (csrc/rollout.hip, csrc/wide_kernels.hip) -------------------------------------------------
+    # the argument lists of rcmarl_policy_probs / rcmarl_rollout_step / rcmarl_rollout_step_episodes, any hid / hid % 32 == 0
+    "rcmarl_policy_probs_wide": [c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_stream],
+    "rcmarl_rollout_step_wide": [c_f32p, c_i32p, c_i32p, c_f32p, C.c_void_p, c_int, c_int, c_f64p, c_f32p, c_f32p, c_f32p,
+                                 c_f32p, c_f32p, c_long, c_long, c_i32p, c_f32p, c_f64p, C.c_double, c_int, c_int, c_float,
+                                 c_int, c_int, c_int, c_int, c_int, c_i32p, c_stream],
+    "rcmarl_rollout_wide_supported": [c_int],
+    # xsT, theta, probs, S, N, E, EP, hid, n_actions, ldp, stream
+    "rcmarl_policy_probs_episodes_wide": [c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_stream],
+    "rcmarl_rollout_step_episodes_wide": [c_f32p, c_i32p, c_i32p, c_f32p, C.c_void_p, c_int, c_int, c_f64p, c_f32p, c_f32p,
+                                          c_f32p, c_f32p, c_f32p, c_long, c_long, c_int, c_i32p, c_f32p, c_f64p, C.c_double,
+                                          c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_stream],
+    # in, in_seed_stride, in_agent_stride, in_row_major, ld_in, dz, theta, m, v, w_off, mask, S, N, B, K, J, ldp, ldb, alpha, 1-b1,
+    # 1-b2, eps, stream
+    "rcmarl_dense_backward_adam": [c_f32p, c_long, c_long, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_i32p, c_int,
+                                   c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_stream],
+    # a2, theta, act_t, delta, ldy, dz3, losspart, S, N, B, in_dim, hid, n_actions, ldp, ldb, stream
+    "rcmarl_wide_actor_head": [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_int, c_stream],
+    # dz1, dz2, dz3, losspart, theta, m, v, mask, loss_out, S, N, B, in_dim, hid, n_actions, ldp, ldb, alpha, 1-b1, 1-b2, eps, stream
+    "rcmarl_wide_actor_small_adam": [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_stream],
     # ---- sharded instance (csrc/shard_pack.hip) ----------------------------------------------------------
     # src, src_batch, ld_src, dst, dst_batch, ld_dst, batches, rows, cols, row_mask, stream
     "rcmarl_copy3d": [c_f32p, c_long, c_long, c_f32p, c_long, c_long, c_int, c_int, c_int, c_i32p, c_stream],
 }
 UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_layout", "rcmarl_lattice_forget", "rcmarl_fit_partial_size", "rcmarl_lattice_set_f16_mode",  "rcmarl_actor_partial_size", "rcmarl_rows_per_chunk", "rcmarl_lattice_f16_mode",
              "rcmarl_wide_grad_size", "rcmarl_wide_rows_per_chunk", "rcmarl_wide_f16_mode", "rcmarl_wide_set_f16_mode",
-             "rcmarl_consensus_params_circulant_supported", "rcmarl_pk_supported", "rcmarl_pk_parts"}
+             "rcmarl_consensus_params_circulant_supported", "rcmarl_pk_supported", "rcmarl_pk_parts",
+             "rcmarl_rollout_wide_supported"}
 
 ERRORS = {1: "RCMARL_ERR_ARG (bad argument)", 2: "RCMARL_ERR_LAUNCH (HIP launch failed)",
           3: "RCMARL_ERR_UNSUPPORTED (shape outside the compiled kernels)"}

@@ -202,11 +202,10 @@ struct ApplySgd {
 struct ApplyAdam {      // TF2 ResourceApplyAdam (see EpiAdam)
   float* m_s; float* v_s; float alpha, one_m_b1, one_m_b2, eps;
   __device__ __forceinline__ void operator()(float* w, long o, float g) const {
-    float mm = m_s[o], vv = v_s[o];
-    mm += (g - mm) * one_m_b1;
-    vv += (g * g - vv) * one_m_b2;
+    float mm = m_s[o], vv = v_s[o], wv = *w;
+    rc_adam_apply(g, wv, mm, vv, alpha, one_m_b1, one_m_b2, eps);
     m_s[o] = mm; v_s[o] = vv;
-    *w = *w - (mm * alpha) / (sqrtf(vv) + eps);
+    *w = wv;
   }
 };
 

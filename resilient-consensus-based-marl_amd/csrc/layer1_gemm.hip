@@ -232,11 +232,10 @@ struct EpiAdam {
       const int agent = n / hid, j = n - agent * hid;
       if (mask == nullptr || mask[agent]) {
         const long o = (long)agent * ldp + (long)m * hid + j;
-        float mm = m_s[o], vv = v_s[o];
-        mm += (g - mm) * one_m_b1;
-        vv += (g * g - vv) * one_m_b2;
+        float mm = m_s[o], vv = v_s[o], w = theta_s[o];
+        rc_adam_apply(g, w, mm, vv, alpha, one_m_b1, one_m_b2, eps);
         m_s[o] = mm; v_s[o] = vv;
-        theta_s[o] = theta_s[o] - (mm * alpha) / (sqrtf(vv) + eps);
+        theta_s[o] = w;
       }
     }
   }

@@ -1483,11 +1483,10 @@ __global__ __launch_bounds__(256) void k_small_adam(const float* __restrict__ pa
     else if (e < PT::gb3) o = g.o_b2 + (e - PT::gb2);
     else if (e < PT::gb1) o = g.o_b3 + (e - PT::gb3);
     else o = g.o_b1 + (e - PT::gb1);
-    float mm = adam_m[ro + o], vv = adam_v[ro + o];
-    mm += (sum - mm) * one_m_b1;
-    vv += (sum * sum - vv) * one_m_b2;
+    float mm = adam_m[ro + o], vv = adam_v[ro + o], w = theta[ro + o];
+    rc_adam_apply(sum, w, mm, vv, alpha, one_m_b1, one_m_b2, eps);
     adam_m[ro + o] = mm; adam_v[ro + o] = vv;
-    theta[ro + o] = theta[ro + o] - (mm * alpha) / (sqrtf(vv) + eps);
+    theta[ro + o] = w;
   }
 }
 

@@ -229,11 +229,10 @@ __global__ __launch_bounds__(256) void k_minibatch_train(MbArgs a) {
         float* vrow = a.adam_v + row * a.ldp;
         for (int e = t; e < g.P; e += 256) {
           const float gr = Gs[e];
-          float mm = mrow[e], vv = vrow[e];
-          mm += (gr - mm) * a.one_m_b1;
-          vv += (gr * gr - vv) * a.one_m_b2;
+          float mm = mrow[e], vv = vrow[e], wv = Ws[e];
+          rc_adam_apply(gr, wv, mm, vv, alpha, a.one_m_b1, a.one_m_b2, a.eps);
           mrow[e] = mm; vrow[e] = vv;
-          Ws[e] = Ws[e] - (mm * alpha) / (sqrtf(vv) + a.eps);
+          Ws[e] = wv;
         }
       } else {
         for (int e = t; e < g.P; e += 256) Ws[e] = Ws[e] - a.lr * Gs[e];

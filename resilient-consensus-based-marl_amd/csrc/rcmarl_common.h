@@ -96,6 +96,16 @@ __device__ __forceinline__ float rc_lrelu(float z) { return z > 0.f ? z : RC_LEA
 // LeakyReLU keeps the sign, so the derivative can be recovered from the activation.
 __device__ __forceinline__ float rc_lrelu_grad_from_act(float a) { return a > 0.f ? 1.f : RC_LEAK; }
 
+// One Adam step of one parameter as TF2's ResourceApplyAdam takes it (Keras 2 `Adam`, the actors' optimiser, reference main.py:64):
+// m += (g - m)(1 - b1); v += (g*g - v)(1 - b2); w -= alpha m / (sqrt(v) + eps), alpha = lr sqrt(1 - b2^t) / (1 - b1^t) formed by the
+// caller.  Epsilon sits OUTSIDE the bias correction.  Every Adam epilogue of the library calls this.
+__device__ __forceinline__ void rc_adam_apply(float g, float& w, float& mm, float& vv, float alpha, float one_m_b1, float one_m_b2,
+                                              float eps) {
+  mm += (g - mm) * one_m_b1;
+  vv += (g * g - vv) * one_m_b2;
+  w = w - (mm * alpha) / (sqrtf(vv) + eps);
+}
+
 __device__ __forceinline__ float rc_wave_sum(float v) {
 #ifdef RCMARL_EMU
   // same xor-butterfly association order, evaluated locally after ONE lane exchange

@@ -31,7 +31,7 @@
 namespace {
 
 constexpr int WBM = 128, WBN = 128, WBK = 16, WLD = 132;
-enum { WEPI_BIAS_LRELU = 0, WEPI_BIAS = 1, WEPI_LRELU_GRAD = 2, WEPI_SGD = 3 };
+enum { WEPI_BIAS_LRELU = 0, WEPI_BIAS = 1, WEPI_LRELU_GRAD = 2, WEPI_SGD = 3, WEPI_ADAM = 4 };
 
 struct WArgs {
   const float* A; long A_zs, A_za; int lda;
@@ -39,6 +39,7 @@ struct WArgs {
   float* C; long C_zs, C_za; int ldc;
   const float* aux; long aux_zs, aux_za; int ldaux;     // bias[m] (BIAS*) or activation(m, n) (LRELU_GRAD)
   const int* mask; float lr;                            // SGD
+  float* am; float* av; float alpha, omb1, omb2, eps;   // ADAM: the slots share C's strides; the accumulator is the gradient
   int M, N, K, NA;
   float sa, sb;                                         // k_wgemm16: power-of-two scales of A and B before the split into f16 pieces
 };
@@ -178,14 +179,16 @@ __device__ __forceinline__ void w_epilogue(const WArgs& a, int s, int ag, int m0
         float* __restrict__ cp = C + (long)(mb + i * 32) * a.ldc + n;
         const float* __restrict__ xp = (EPI == WEPI_LRELU_GRAD) ? aux + (long)(mb + i * 32) * a.ldaux + n : nullptr;
         float old[16];
-        if (EPI == WEPI_LRELU_GRAD || EPI == WEPI_SGD) {
+        if (EPI == WEPI_LRELU_GRAD || EPI == WEPI_SGD || EPI == WEPI_ADAM) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int dr = (r & 3) + 8 * (r >> 2);
             const bool ok = FULL || mb + i * 32 + dr < a.M;
-            old[r] = !ok ? 0.f : (EPI == WEPI_SGD ? cp[(long)dr * a.ldc] : xp[(long)dr * a.ldaux]);
+            old[r] = !ok ? 0.f : (EPI == WEPI_LRELU_GRAD ? xp[(long)dr * a.ldaux] : cp[(long)dr * a.ldc]);
           }
         }
+        float* __restrict__ mp = (EPI == WEPI_ADAM) ? a.am + s * a.C_zs + ag * a.C_za + (long)(mb + i * 32) * a.ldc + n : nullptr;
+        float* __restrict__ vp = (EPI == WEPI_ADAM) ? a.av + s * a.C_zs + ag * a.C_za + (long)(mb + i * 32) * a.ldc + n : nullptr;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int dr = (r & 3) + 8 * (r >> 2);
@@ -195,7 +198,12 @@ __device__ __forceinline__ void w_epilogue(const WArgs& a, int s, int ag, int m0
           if (EPI == WEPI_BIAS_LRELU) o = rc_lrelu(v + bias[i][r]);
           else if (EPI == WEPI_BIAS) o = v + bias[i][r];
           else if (EPI == WEPI_LRELU_GRAD) o = v * rc_lrelu_grad_from_act(old[r]);
-          else o = old[r] - a.lr * v;
+          else if (EPI == WEPI_ADAM) {
+            float mm = mp[(long)dr * a.ldc], vv = vp[(long)dr * a.ldc];
+            o = old[r];
+            rc_adam_apply(v, o, mm, vv, a.alpha, a.omb1, a.omb2, a.eps);
+            mp[(long)dr * a.ldc] = mm; vp[(long)dr * a.ldc] = vv;
+          } else o = old[r] - a.lr * v;
           cp[(long)dr * a.ldc] = o;
         }
       }
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(256, 3) void k_wgemm(const WArgs a) {      // 3 wor
   __shared__ __attribute__((aligned(16))) float sA[2 * WBK * WLD];
   __shared__ __attribute__((aligned(16))) float sB[2 * WBK * WLD];
   const int z = blockIdx.z, s = z / a.NA, ag = z - s * a.NA;
-  if (EPI == WEPI_SGD && a.mask && !a.mask[ag]) return;        // workgroup-uniform
+  if ((EPI == WEPI_SGD || EPI == WEPI_ADAM) && a.mask && !a.mask[ag]) return;        // workgroup-uniform
   const int m0 = blockIdx.y * WBM, n0 = blockIdx.x * WBN;
   rc_f32x16 acc[2][2];
   w_loop_f32<A_KC, B_KC, VEC>(a, a.A + s * a.A_zs + ag * a.A_za, a.B + s * a.B_zs + ag * a.B_za, m0, n0, sA, sB, acc);
@@ -323,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void k_wgemm16(const WArgs a) {
     wq = blockIdx.x - z * per;
   }
   const int s = z / a.NA, ag = z - s * a.NA;
-  if (EPI == WEPI_SGD && a.mask && !a.mask[ag]) return;        // workgroup-uniform
+  if ((EPI == WEPI_SGD || EPI == WEPI_ADAM) && a.mask && !a.mask[ag]) return;        // workgroup-uniform
   const int m0 = (wq % tm) * WBM, n0 = (wq / tm) * WBN;
   const float* __restrict__ A = a.A + s * a.A_zs + ag * a.A_za;
   const float* __restrict__ Bp = a.B + s * a.B_zs + ag * a.B_za;
@@ -679,6 +687,90 @@ __global__ __launch_bounds__(256) void k_whead_apply(const float* __restrict__ g
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Wide actor (hid != 20): the head of actor_update (agents/resilient_CAC_agents.py:86-101, one train_on_batch(s, a,
+// sample_weight=td) step) -- what k_mid_actor (mid_kernels.hip) does for 20 units, on the feature-major layer-2 activations.
+// Column pass, one thread per row b: logits, log-softmax, dz3[a][b] = (p_a - [a == label]) * w_b / B (Keras's sample-weighted
+// SUM_OVER_BATCH_SIZE reduction divides by the batch size, not by the weight sum), loss part of the chunk = sum_b nll_b w_b.
+__global__ __launch_bounds__(256) void k_wactor_head(const float* __restrict__ a2, const float* __restrict__ theta,
+                                                     const float* __restrict__ act_t, const float* __restrict__ delta, int ldy,
+                                                     float* __restrict__ dz3, float* __restrict__ losspart, int N, int B,
+                                                     int in_dim, int hid, int ldp, int ldb, int nchunk) {
+  constexpr int A = 5;
+  __shared__ float red[4];
+  const int s = blockIdx.z, i = blockIdx.y, b = blockIdx.x * WROWS + threadIdx.x;
+  const bool valid = b < B;
+  const NetGeom g = make_geom(in_dim, hid, A);
+  const float* __restrict__ th = theta + ((long)s * N + i) * ldp;
+  const float* __restrict__ col = a2 + ((long)s * N + i) * hid * ldb + (valid ? b : 0);
+  float logit[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) logit[a] = 0.f;
+  for (int k = 0; k < hid; ++k) {
+    const float v = col[(long)k * ldb];
+#pragma unroll
+    for (int a = 0; a < A; ++a) logit[a] = fmaf(v, th[g.o_W3 + k * A + a], logit[a]);
+  }
+#pragma unroll
+  for (int a = 0; a < A; ++a) logit[a] += th[g.o_b3 + a];
+  float mx = logit[0];
+#pragma unroll
+  for (int a = 1; a < A; ++a) mx = fmaxf(mx, logit[a]);
+  float se = 0.f;
+#pragma unroll
+  for (int a = 0; a < A; ++a) se += expf(logit[a] - mx);
+  const float lse = logf(se);
+  const long o = ((long)s * N + i) * ldy + b;
+  const int label = valid ? (int)act_t[o] : 0;
+  const float w = valid ? delta[o] : 0.f;
+  const float wB = w / (float)B;
+  float nll = 0.f;
+#pragma unroll
+  for (int a = 0; a < A; ++a) {
+    const float logp = (logit[a] - mx) - lse;
+    if (a == label) nll = -logp;
+    if (valid) dz3[(((long)s * N + i) * A + a) * ldb + b] = (expf(logp) - (a == label ? 1.f : 0.f)) * wB;
+  }
+  const float part = rc_wave_sum(nll * w);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) losspart[((long)s * N + i) * nchunk + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// b1, b2, b3 of a wide actor: gradient = row sum of dz1 / dz2 / dz3 (one wavefront per bias), then the Adam step; loss = sum of
+// the head's chunk parts / B
+__global__ __launch_bounds__(256) void k_wactor_small_adam(const float* __restrict__ dz1, const float* __restrict__ dz2,
+                                                           const float* __restrict__ dz3, const float* __restrict__ losspart,
+                                                           float* __restrict__ theta, float* __restrict__ adam_m,
+                                                           float* __restrict__ adam_v, const int* __restrict__ mask,
+                                                           float* __restrict__ loss_out, int N, int B, int in_dim, int hid, int ldp,
+                                                           int ldb, int nchunk, float alpha, float omb1, float omb2, float eps) {
+  constexpr int A = 5;
+  const int s = blockIdx.z, i = blockIdx.y, e = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (loss_out && blockIdx.x == 0 && threadIdx.x == 0) {
+    float sum = 0.f;
+    for (int c = 0; c < nchunk; ++c) sum += losspart[((long)s * N + i) * nchunk + c];
+    loss_out[(long)s * N + i] = sum / (float)B;
+  }
+  if (e >= 2 * hid + A || (mask && !mask[i])) return;
+  const NetGeom g = make_geom(in_dim, hid, A);
+  const long z = (long)s * N + i;
+  const float* __restrict__ row;
+  int o;
+  if (e < hid) { row = dz1 + (z * hid + e) * ldb; o = g.o_b1 + e; }
+  else if (e < 2 * hid) { row = dz2 + (z * hid + (e - hid)) * ldb; o = g.o_b2 + (e - hid); }
+  else { row = dz3 + (z * A + (e - 2 * hid)) * ldb; o = g.o_b3 + (e - 2 * hid); }
+  float acc = 0.f;
+  for (int b = l; b < B; b += 64) acc += row[b];
+  acc = rc_wave_sum(acc);
+  if (l == 0) {
+    const long q = z * ldp + o;
+    float w = theta[q], mm = adam_m[q], vv = adam_v[q];
+    rc_adam_apply(acc, w, mm, vv, alpha, omb1, omb2, eps);
+    theta[q] = w; adam_m[q] = mm; adam_v[q] = vv;
+  }
+}
+
 static inline bool w_dims_ok(int S, int N, int B, int K, int J, int ldp, int ldb) {
   return S > 0 && N > 0 && B > 0 && K > 0 && J > 0 && ldp > 0 && ldb >= B;
 }
@@ -853,5 +945,51 @@ RCMARL_EXPORT int rcmarl_wide_head_apply(const float* grads, float* theta, const
                                          int in_dim, int hid, int ldp, void* stream) {
   if (!grads || !theta || !coop || S <= 0 || N <= 0 || B <= 0 || hid <= 0) return RCMARL_ERR_ARG;
   RCMARL_LAUNCH(k_whead_apply, dim3(N, S), dim3(256), 0, stream, grads, theta, coop, N, B, in_dim, hid, ldp);
+  return rcmarl_check_launch();
+}
+
+// ---- wide actor update (agents/resilient_CAC_agents.py:86-101) -------------------------------------------------------------
+// W[k][j], m, v <- Adam(W, m, v, g[k][j] = sum_b in(k, b) dz[j][b]): the weight-gradient GEMM of rcmarl_dense_backward_sgd with the
+// Adam step as its epilogue (alpha = lr sqrt(1 - b2^t) / (1 - b1^t) from the caller).  adam_m / adam_v: [S][N][ldp] like theta.
+RCMARL_EXPORT int rcmarl_dense_backward_adam(const float* in, long in_seed_stride, long in_agent_stride, int in_row_major,
+                                             int ld_in, const float* dz, float* theta, float* adam_m, float* adam_v, int w_off,
+                                             const int* mask, int S, int N, int B, int K, int J, int ldp, int ldb, float alpha,
+                                             float one_m_b1, float one_m_b2, float eps, void* stream) {
+  if (!in || !dz || !theta || !adam_m || !adam_v || !w_dims_ok(S, N, B, K, J, ldp, ldb) || w_off < 0 || ld_in <= 0)
+    return RCMARL_ERR_ARG;
+  WArgs a{};
+  a.A = in; a.A_zs = in_seed_stride; a.A_za = in_agent_stride; a.lda = ld_in;           // A(m=k, kk=b)
+  a.B = dz; a.B_zs = (long)N * J * ldb; a.B_za = (long)J * ldb; a.ldb = ldb;            // B(kk=b, n=j) = dz[j*ldb + b]
+  a.C = theta + w_off; a.C_zs = (long)N * ldp; a.C_za = ldp; a.ldc = J;
+  a.am = adam_m + w_off; a.av = adam_v + w_off;
+  a.mask = mask; a.alpha = alpha; a.omb1 = one_m_b1; a.omb2 = one_m_b2; a.eps = eps;
+  a.M = K; a.N = J; a.K = B; a.NA = N;
+  a.sa = in_row_major ? 0.f : RC_W16_ACT_SCALE; a.sb = RC_F16_DZ_SCALE;   // activations (feature-major) x dz
+  return in_row_major ? w_launch<false, true, WEPI_ADAM>(a, S, stream) : w_launch<true, true, WEPI_ADAM>(a, S, stream);
+}
+
+// a2: layer-2 activations [S][N*hid][ldb]; act_t, delta: labels and sample weights [S][N][ldy]; dz3: [S][N*5][ldb] (out);
+// losspart: [S][N][ceil(B / rows_per_chunk)] (out)
+RCMARL_EXPORT int rcmarl_wide_actor_head(const float* a2, const float* theta, const float* act_t, const float* delta, int ldy,
+                                         float* dz3, float* losspart, int S, int N, int B, int in_dim, int hid, int n_actions,
+                                         int ldp, int ldb, void* stream) {
+  if (!a2 || !theta || !act_t || !delta || !dz3 || !losspart || !w_dims_ok(S, N, B, in_dim, hid, ldp, ldb) || ldy < B)
+    return RCMARL_ERR_ARG;
+  if (n_actions != 5) return RCMARL_ERR_UNSUPPORTED;
+  const int nchunk = rc_ceil_div(B, WROWS);
+  RCMARL_LAUNCH(k_wactor_head, dim3(nchunk, N, S), dim3(256), 0, stream, a2, theta, act_t, delta, ldy, dz3, losspart, N, B, in_dim,
+                hid, ldp, ldb, nchunk);
+  return rcmarl_check_launch();
+}
+
+RCMARL_EXPORT int rcmarl_wide_actor_small_adam(const float* dz1, const float* dz2, const float* dz3, const float* losspart,
+                                               float* theta, float* adam_m, float* adam_v, const int* mask, float* loss_out,
+                                               int S, int N, int B, int in_dim, int hid, int n_actions, int ldp, int ldb,
+                                               float alpha, float one_m_b1, float one_m_b2, float eps, void* stream) {
+  if (!dz1 || !dz2 || !dz3 || !losspart || !theta || !adam_m || !adam_v || !w_dims_ok(S, N, B, in_dim, hid, ldp, ldb))
+    return RCMARL_ERR_ARG;
+  if (n_actions != 5) return RCMARL_ERR_UNSUPPORTED;
+  RCMARL_LAUNCH(k_wactor_small_adam, dim3(rc_ceil_div(2 * hid + 5, 4), N, S), dim3(256), 0, stream, dz1, dz2, dz3, losspart, theta,
+                adam_m, adam_v, mask, loss_out, N, B, in_dim, hid, ldp, ldb, rc_ceil_div(B, WROWS), alpha, one_m_b1, one_m_b2, eps);
   return rcmarl_check_launch();
 }

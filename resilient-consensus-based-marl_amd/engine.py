@@ -65,7 +65,7 @@ class EngineConfig:
     def __init__(self, n_agents, agent_label, in_nodes, H=0, gamma=0.9, slow_lr=0.002, fast_lr=0.01, n_actions=5,
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
-                 local_fit_steps=5, lattice="auto", critic_hid=HID):
+                 local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -79,6 +79,9 @@ class EngineConfig:
         # hidden width of the critic (the reference builds 20-unit networks, main.py:59-82; BASELINE configs[4] widens
         # the critic to 512 units): any other width runs the dense-GEMM path of csrc/wide_kernels.hip
         self.critic_hid = int(critic_hid)
+        # hidden width of the actors: any other width than the reference's 20 takes the wide-actor kernels (rollout:
+        # csrc/rollout.hip, Adam step: the dense GEMMs of csrc/wide_kernels.hip with an Adam epilogue)
+        self.actor_hid = int(actor_hid)
         assert len(self.agent_label) == self.n_agents and len(self.in_nodes) == self.n_agents
         if np.ndim(H) == 0:
             self.H_per_agent = [int(H)] * self.n_agents
@@ -107,6 +110,15 @@ class EngineConfig:
                 raise ValueError("unknown agent label %r" % lab)
         if self.critic_hid < 1:
             raise ValueError("critic_hid must be positive")
+        if self.actor_hid < 1:
+            raise ValueError("actor_hid must be positive")
+        if self.actor_hid != HID:
+            if any(lab != COOP for lab in self.agent_label):
+                raise ValueError("a wide actor (actor_hid = %d) needs an all-cooperative team: the Greedy / Malicious / Faulty agents' "
+                                 "mini-batch chains (csrc/minibatch_fit.hip) are compiled for 20 units" % self.actor_hid)
+            if not self.regular:
+                raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit actor (actor_hid = %d)"
+                                 % self.actor_hid)
         if not self.regular and self.critic_hid != HID:
             raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit critic: the wide head's gather / "
                              "GEMM / select chain is sized by one d (critic_hid = %d)" % self.critic_hid)
@@ -144,8 +156,8 @@ class RPBCACEngine:
         S, N = c.n_seeds, c.n_agents
         self.S, self.N = S, N
         self.in_c, self.in_r = N * c.n_states, N * (c.n_states + 1)
-        self.hid = {"actor": HID, "critic": c.critic_hid, "tr": HID}
-        self.P = {"actor": net_numel(self.in_c, c.n_actions), "critic": net_numel(self.in_c, 1, c.critic_hid),
+        self.hid = {"actor": c.actor_hid, "critic": c.critic_hid, "tr": HID}
+        self.P = {"actor": net_numel(self.in_c, c.n_actions, c.actor_hid), "critic": net_numel(self.in_c, 1, c.critic_hid),
                   "tr": net_numel(self.in_r, 1)}
         self.in_dim = {"actor": self.in_c, "critic": self.in_c, "tr": self.in_r}
         self.out_dim = {"actor": c.n_actions, "critic": 1, "tr": 1}
@@ -167,6 +179,10 @@ class RPBCACEngine:
         self.a1_cached = {"critic": False, "tr": False}
         self.a2_cached = False                # wide critic: self.w_a2 holds the fp32 layer-2 activations of the LIVE critic on the s rows
         self._graphs, self.graph_captures, self.graph_replays = {}, 0, 0       # captured update epochs (see _epoch)
+        # wide actor: the episode-parallel rollout runs on the matrix-core kernel where it serves the width, else episode by episode
+        # on the plain kernel (rcmarl_rollout_step_wide)
+        self.actor_wide = c.actor_hid != HID
+        self.actor_mx = bool(self.actor_wide and lib.rcmarl_rollout_wide_supported(c.actor_hid))
         self.loss = {k: torch.zeros(S, N, **f32) for k in ("actor", "critic", "tr")}
         self.rp, self.ybuf = None, {k: None for k in ("r_fit", "y_c", "v_tr", "v_next", "v_cur", "delta", "act_t")}
         self._alloc_row_buffers(c.buffer_size + self.n_last)
@@ -289,7 +305,7 @@ class RPBCACEngine:
         gradient records and the neighbour-estimate matrix of the consensus step."""
         self.wide = self.hid["critic"] != HID
         if not self.wide:
-            return
+            return self._init_wide_actor()
         S, N, L, hid, d = self.S, self.N, self.lib, self.hid["critic"], self.cfg.d
         f32 = dict(dtype=torch.float32, device=self.dev)
         assert self.ldb >= self.EP_pad()
@@ -299,6 +315,26 @@ class RPBCACEngine:
         self.w_losspart = torch.zeros(S, N, (self.cap + L.rcmarl_wide_rows_per_chunk() - 1) // L.rcmarl_wide_rows_per_chunk(), **f32)
         self.w_hmat, self.w_hb = torch.zeros(S, N, d + 1, hid, **f32), torch.zeros(S, N, d + 1, **f32)
         self.w_est = torch.zeros(S, N, d + 1, self.ldb, **f32)
+        self._init_wide_actor()
+
+    def _init_wide_actor(self):
+        """Scratch of the wide actor's Adam step, sized by the n_last rows it runs on: a1, a2 / dz1, dz2 ([S][N*hid][ldn]), dz3
+        ([S][N*5][ldn]) and the loss parts.  The three activation-sized buffers are views into the wide critic's (w_a1, w_a2, w_dz1:
+        dead by the time the actor step runs) when those are large enough, else the actor's own."""
+        if not self.actor_wide:
+            return
+        S, N, L, hid = self.S, self.N, self.lib, self.hid["actor"]
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.wa_ldn = ldn = pad64(self.n_last)
+        need = S * N * hid * ldn
+        if self.wide and self.w_a1.numel() >= need:
+            self.wa_alias = True
+            self.wa_a1, self.wa_a2, self.wa_dz = (t.view(-1)[:need].view(S, N * hid, ldn) for t in (self.w_a1, self.w_a2, self.w_dz1))
+        else:
+            self.wa_alias = False
+            self.wa_a1, self.wa_a2, self.wa_dz = (torch.zeros(S, N * hid, ldn, **f32) for _ in range(3))
+        self.wa_dz3 = torch.zeros(S, N * self.cfg.n_actions, ldn, **f32)
+        self.wa_losspart = torch.zeros(S, N, (self.n_last + L.rcmarl_wide_rows_per_chunk() - 1) // L.rcmarl_wide_rows_per_chunk(), **f32)
 
     def EP_pad(self):
         return pad64(self.cfg.n_ep_fixed)
@@ -524,6 +560,9 @@ class RPBCACEngine:
         if not self.cfg.regular:
             raise ValueError("agent sharding needs a regular communication graph with one H: the column-sharded consensus "
                              "(parallel.ShardedConsensus) takes one (d, H)")
+        if self.actor_wide:
+            raise ValueError("agent sharding keeps the actors replicated on the 20-unit kernels: a wide actor (actor_hid = %d) "
+                             "is not sharded" % self.cfg.actor_hid)
         if comm is None and world is None:
             comm = TorchComm(group)
         if comm is not None:
@@ -860,7 +899,7 @@ class RPBCACEngine:
             sd[k] = getattr(self, k).detach().cpu()
         if hasattr(self, "adv"):
             sd["adv"] = self.adv.state_dict()
-        sd["shape"] = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
+        sd["shape"] = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "actor_hid": c.actor_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
                        "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
         if self.np_rngs is not None:          # plain tensors / numbers only, so the file loads with weights_only=True
             sd["np_rngs"] = []
@@ -876,9 +915,10 @@ class RPBCACEngine:
             raise ValueError("checkpoint does not match this engine (format/S/N/agent labels)")
         if [list(map(int, r)) for r in sd["in_nodes"]] != c.in_nodes:
             raise ValueError("checkpoint was written for a different communication graph")
-        mine = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
-                "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
-        theirs = sd.get("shape", mine)
+        mine = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "actor_hid": c.actor_hid, "buffer_size": c.buffer_size,
+                "n_ep_fixed": c.n_ep_fixed, "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
+        theirs = dict(sd.get("shape", mine))
+        theirs.setdefault("actor_hid", HID)              # files written before actors could be wide
         diff = {k: (theirs.get(k), v) for k, v in mine.items() if theirs.get(k) != v}
         if "H" in diff and self._H_list(theirs.get("H")) == c.H_per_agent:      # the same per-agent H, written the other way
             del diff["H"]
@@ -974,15 +1014,17 @@ class RPBCACEngine:
             cur, nxt = self.cur, 1 - self.cur
             row = self.B + j
             if c.rng_mode == "device":
-                L.rcmarl_rollout_step(self.xs[cur].data_ptr(), self.pos[cur].data_ptr(), self.goal.data_ptr(),
-                                      self.theta["actor"].data_ptr(), self.seeds_dev.data_ptr(), c.nrow, c.ncol,
-                                      self.scale.data_ptr(), rp[0], rp[1], rp[2], rp[3], rp[4], self.cap, row,
-                                      self.pos[nxt].data_ptr(), self.xs[nxt].data_ptr(), self.ret.data_ptr(),
-                                      self.gpow[j], self.episode, j, c.mu, S, N, HID, c.n_actions, self.ldp["actor"],
-                                      None, self.stream)
+                step_fn = L.rcmarl_rollout_step_wide if self.actor_wide else L.rcmarl_rollout_step
+                step_fn(self.xs[cur].data_ptr(), self.pos[cur].data_ptr(), self.goal.data_ptr(),
+                        self.theta["actor"].data_ptr(), self.seeds_dev.data_ptr(), c.nrow, c.ncol,
+                        self.scale.data_ptr(), rp[0], rp[1], rp[2], rp[3], rp[4], self.cap, row,
+                        self.pos[nxt].data_ptr(), self.xs[nxt].data_ptr(), self.ret.data_ptr(),
+                        self.gpow[j], self.episode, j, c.mu, S, N, self.hid["actor"], c.n_actions, self.ldp["actor"],
+                        None, self.stream)
             else:
-                L.rcmarl_policy_probs(self.xs[cur].data_ptr(), self.theta["actor"].data_ptr(), self.probs.data_ptr(), S, N,
-                                      self.in_c, HID, c.n_actions, self.ldp["actor"], self.stream)
+                probs_fn = L.rcmarl_policy_probs_wide if self.actor_wide else L.rcmarl_policy_probs
+                probs_fn(self.xs[cur].data_ptr(), self.theta["actor"].data_ptr(), self.probs.data_ptr(), S, N,
+                         self.in_c, self.hid["actor"], c.n_actions, self.ldp["actor"], self.stream)
                 probs = self.probs.detach().cpu().numpy()
                 acts = np.zeros((S, N), np.int32)
                 for s in range(S):                                    # get_action(): agents/...:208-219
@@ -1027,14 +1069,15 @@ class RPBCACEngine:
                                          n_eps, EP, HID, self.ldp["critic"], self.stream)
         rp = self._replay_ptrs()
         cur = 0
+        step_fn = L.rcmarl_rollout_step_episodes_wide if self.actor_wide else L.rcmarl_rollout_step_episodes
         for j in range(c.max_ep_len):
             nxt = 1 - cur
-            L.rcmarl_rollout_step_episodes(self.xsT[cur].data_ptr(), self.posT[cur].data_ptr(), self.goal.data_ptr(),
-                                           self.theta["actor"].data_ptr(), self.seeds_dev.data_ptr(), c.nrow, c.ncol,
-                                           self.scale.data_ptr(), rp[0], rp[1], rp[2], rp[3], rp[4], self.cap, self.B,
-                                           c.max_ep_len, self.posT[nxt].data_ptr(), self.xsT[nxt].data_ptr(),
-                                           self.retT.data_ptr(), self.gpow[j], self.episode, j, c.mu, S, N, n_eps, EP, HID,
-                                           c.n_actions, self.ldp["actor"], self.stream)
+            step_fn(self.xsT[cur].data_ptr(), self.posT[cur].data_ptr(), self.goal.data_ptr(),
+                    self.theta["actor"].data_ptr(), self.seeds_dev.data_ptr(), c.nrow, c.ncol,
+                    self.scale.data_ptr(), rp[0], rp[1], rp[2], rp[3], rp[4], self.cap, self.B,
+                    c.max_ep_len, self.posT[nxt].data_ptr(), self.xsT[nxt].data_ptr(),
+                    self.retT.data_ptr(), self.gpow[j], self.episode, j, c.mu, S, N, n_eps, EP,
+                    self.hid["actor"], c.n_actions, self.ldp["actor"], self.stream)
             cur = nxt
         self.B += c.max_ep_len * n_eps
         self.ret_hist[:n_eps].copy_(self.retT[:, :, :n_eps].permute(2, 0, 1))
@@ -1522,6 +1565,8 @@ class RPBCACEngine:
         b1, b2, eps = 0.9, 0.999, 1e-7
         alpha = float(np.float32(c.slow_lr * math.sqrt(1.0 - b2 ** self.adam_t) / (1.0 - b1 ** self.adam_t)))
         omb1, omb2, epsf = float(np.float32(1 - b1)), float(np.float32(1 - b2)), float(np.float32(eps))
+        if self.actor_wide:
+            return self._actor_step_wide(nl, row0, alpha, omb1, omb2, epsf)
         self._layer1("s", self.theta["actor"], "actor", nl, row0)
         L.rcmarl_mid_actor(self.a1t.data_ptr(), self.theta["actor"].data_ptr(), self.ybuf["act_t"].data_ptr(),
                            self.ybuf["delta"].data_ptr(), self.partials.data_ptr(), S, N, nl, self.in_c, HID, c.n_actions,
@@ -1533,6 +1578,39 @@ class RPBCACEngine:
         L.rcmarl_layer1_backward_adam(sptr, sstride, self.a1t.data_ptr(), self.theta["actor"].data_ptr(),
                                       self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.coop.data_ptr(), S, N, nl,
                                       self.in_c, HID, self.ldp["actor"], self.ldb, alpha, omb1, omb2, epsf, self.stream)
+
+    def _actor_step_wide(self, nl, row0, alpha, omb1, omb2, epsf):
+        """The Adam step of _actor_update for a wide actor: every layer a dense GEMM per agent (csrc/wide_kernels.hip), the Adam
+        arithmetic in the weight-gradient GEMMs' epilogue.  Every gradient is formed from pre-step weights: a layer's weights are
+        stepped only after the backward-data GEMM that reads them (W3 after dz2, W2 after dz1); the biases last."""
+        c, L, S, N, hid, st = self.cfg, self.lib, self.S, self.N, self.hid["actor"], self.stream
+        th, m, v, ldp, ldn, A = self.theta["actor"], self.adam_m, self.adam_v, self.ldp["actor"], self.wa_ldn, c.n_actions
+        a1, a2, dz, dz3 = self.wa_a1, self.wa_a2, self.wa_dz, self.wa_dz3
+        o_b1, o_W2, o_b2 = self._wide_offsets("actor")
+        o_W3 = o_b2 + hid
+        if self.wa_alias:
+            self.a2_cached = False                # (w_a2 now holds the actor's activations)
+        sptr, sstride = self._x("s", row0)
+        adam = (alpha, omb1, omb2, epsf, st)
+        L.rcmarl_dense_forward(sptr, sstride, 0, 1, self.in_c, th.data_ptr(), 0, o_b1, a1.data_ptr(), S, N, nl, self.in_c, hid, ldp,
+                               ldn, st)
+        L.rcmarl_dense_forward(a1.data_ptr(), N * hid * ldn, hid * ldn, 0, ldn, th.data_ptr(), o_W2, o_b2, a2.data_ptr(), S, N, nl,
+                               hid, hid, ldp, ldn, st)
+        L.rcmarl_wide_actor_head(a2.data_ptr(), th.data_ptr(), self.ybuf["act_t"].data_ptr(), self.ybuf["delta"].data_ptr(), self.ldb,
+                                 dz3.data_ptr(), self.wa_losspart.data_ptr(), S, N, nl, self.in_c, hid, A, ldp, ldn, st)
+        # dz2 = (W3 dz3) * lrelu'(a2) -> dz; then W3 may step (gradient a2 dz3^T)
+        L.rcmarl_dense_backward_data(dz3.data_ptr(), th.data_ptr(), o_W3, a2.data_ptr(), dz.data_ptr(), S, N, nl, hid, A, ldp, ldn, st)
+        L.rcmarl_dense_backward_adam(a2.data_ptr(), N * hid * ldn, hid * ldn, 0, ldn, dz3.data_ptr(), th.data_ptr(), m.data_ptr(),
+                                     v.data_ptr(), o_W3, self.coop.data_ptr(), S, N, nl, hid, A, ldp, ldn, *adam)
+        # dz1 = (W2 dz2) * lrelu'(a1) -> the buffer a2 held; then W2 (a1 dz2^T) and W1 (x^T dz1^T) step
+        L.rcmarl_dense_backward_data(dz.data_ptr(), th.data_ptr(), o_W2, a1.data_ptr(), a2.data_ptr(), S, N, nl, hid, hid, ldp, ldn, st)
+        L.rcmarl_dense_backward_adam(a1.data_ptr(), N * hid * ldn, hid * ldn, 0, ldn, dz.data_ptr(), th.data_ptr(), m.data_ptr(),
+                                     v.data_ptr(), o_W2, self.coop.data_ptr(), S, N, nl, hid, hid, ldp, ldn, *adam)
+        L.rcmarl_dense_backward_adam(sptr, sstride, 0, 1, self.in_c, a2.data_ptr(), th.data_ptr(), m.data_ptr(), v.data_ptr(), 0,
+                                     self.coop.data_ptr(), S, N, nl, self.in_c, hid, ldp, ldn, *adam)
+        L.rcmarl_wide_actor_small_adam(a2.data_ptr(), dz.data_ptr(), dz3.data_ptr(), self.wa_losspart.data_ptr(), th.data_ptr(),
+                                       m.data_ptr(), v.data_ptr(), self.coop.data_ptr(), self.loss["actor"].data_ptr(), S, N, nl,
+                                       self.in_c, hid, A, ldp, ldn, *adam)
 
     # adversaries (agents/adversarial_CAC_agents.py) are handled by engine_adversaries.py
     def _require_adversary_support(self):
@@ -1576,14 +1654,19 @@ class RPBCACEngine:
         if self.profile_phases:
             self.sync()
             t0 = time.perf_counter()
-        if c.rng_mode == "device":
-            self.rollout_block(c.n_ep_fixed)
-        else:
-            for e in range(c.n_ep_fixed):
-                self.rollout_episode(e)
+        self._rollout(c.n_ep_fixed)
         self._timed("rollout", t0)
         self.update_block()
         return self.episode_logs(c.n_ep_fixed)
+
+    def _rollout(self, n_eps):
+        """n_eps episodes: stepped together on the device stream (rng_mode 'device'; a wide actor only where the matrix-core
+        kernel serves its width -- the same draws and rows come out episode by episode on the plain kernel), else one by one."""
+        if self.cfg.rng_mode == "device" and (not self.actor_wide or self.actor_mx):
+            self.rollout_block(n_eps)
+        else:
+            for e in range(n_eps):
+                self.rollout_episode(e)
 
     def episode_logs(self, n_eps):
         """Episode summaries exactly as train_agents.py:168-180 computes them (float64
@@ -1663,11 +1746,7 @@ class RPBCACEngine:
                 team, adv, est = self.run_block()
                 self._warn_if_diverged()
             else:                               # trailing episodes without an update (t % n_ep_fixed never hits)
-                if c.rng_mode == "device":
-                    self.rollout_block(n)
-                else:
-                    for e in range(n):
-                        self.rollout_episode(e)
+                self._rollout(n)
                 team, adv, est = self.episode_logs(n)
             logs["True_team_returns"].append(team)
             logs["True_adv_returns"].append(adv)

@@ -5,6 +5,7 @@
     python tools/kbench.py k1        # consensus_params at (d,H) = (4,1), (10,4), (18,8)
     python tools/kbench.py k1_ragged # consensus_params_ragged on a degree mix against one masked uniform launch per class
     python tools/kbench.py mid       # mid_fit / consensus_head / mid_value
+    python tools/kbench.py rollout_wide  # wide actor: one step of 50 episodes, matrix-core kernel vs plain kernel vs the weight stream
 """
 import os
 import sys
@@ -533,8 +534,55 @@ def pk(L, S=1, N=int(os.environ.get("RCMARL_KBENCH_N", "256")), B=3000, width=2,
     print("one SGD step, %d agents: %.2f ms  -> 1024 agents: %.1f ms" % (N, tot / 1e3, tot / 1e3 * 1024 / N))
 
 
+def rollout_wide(L, S=1, N=int(os.environ.get("RCMARL_KBENCH_N", "1024")), hid=512, E=50, nrow=32):
+    """one environment step of E episodes with a wide actor: the matrix-core kernel (rcmarl_rollout_step_episodes_wide) against the
+    plain kernel stepping the episodes one by one (rcmarl_rollout_step_wide, the yardstick) and against the time to stream the
+    actor weights once at 8 TB/s (the bound)"""
+    st = torch.cuda.current_stream().cuda_stream
+    in_dim, A, EP = 2 * N, 5, pad64(E)
+    P = in_dim * hid + hid + hid * hid + hid + hid * A + A
+    ldp = pad64(P)
+    theta = torch.empty(S, N, ldp, device="cuda").uniform_(-0.04, 0.04)
+    goal = torch.randint(0, nrow, (S, N, 2), dtype=torch.int32, device="cuda")
+    seeds = torch.arange(1, S + 1, dtype=torch.int64, device="cuda")
+    mean, std = (nrow - 1) / 2.0, float(np.std(np.arange(nrow)))
+    scale = torch.tensor([mean, mean, std, std], dtype=torch.float64, device="cuda")
+    cap = E + 8
+    rp = [torch.zeros(S, cap, w * N, device="cuda") for w in (2, 2, 3, 1, 1)]
+    posT = [torch.zeros(S, N, 2, EP, dtype=torch.int32, device="cuda") for _ in range(2)]
+    xsT = [torch.zeros(S, 2 * N, EP, device="cuda") for _ in range(2)]
+    retT = torch.zeros(S, N, EP, dtype=torch.float64, device="cuda")
+    L.rcmarl_env_reset_episodes(None, seeds.data_ptr(), nrow, nrow, scale.data_ptr(), 0, posT[0].data_ptr(), xsT[0].data_ptr(),
+                                retT.data_ptr(), S, N, E, EP, st)
+    pos = [torch.zeros(S, N, 2, dtype=torch.int32, device="cuda") for _ in range(2)]
+    xs = [torch.zeros(S, 2 * N, device="cuda") for _ in range(2)]
+    ret = torch.zeros(S, N, dtype=torch.float64, device="cuda")
+    L.rcmarl_env_reset(None, seeds.data_ptr(), nrow, nrow, scale.data_ptr(), 0, pos[0].data_ptr(), xs[0].data_ptr(), ret.data_ptr(), S, N, st)
+    r = [t.data_ptr() for t in rp]
+
+    def mx():
+        L.rcmarl_rollout_step_episodes_wide(xsT[0].data_ptr(), posT[0].data_ptr(), goal.data_ptr(), theta.data_ptr(), seeds.data_ptr(), nrow,
+                                            nrow, scale.data_ptr(), r[0], r[1], r[2], r[3], r[4], cap, 0, 1, posT[1].data_ptr(),
+                                            xsT[1].data_ptr(), retT.data_ptr(), 1.0, 0, 0, 0.1, S, N, E, EP, hid, A, ldp, st)
+
+    def plain():
+        for e in range(E):
+            L.rcmarl_rollout_step_wide(xs[0].data_ptr(), pos[0].data_ptr(), goal.data_ptr(), theta.data_ptr(), seeds.data_ptr(), nrow, nrow,
+                                       scale.data_ptr(), r[0], r[1], r[2], r[3], r[4], cap, e, pos[1].data_ptr(), xs[1].data_ptr(),
+                                       ret.data_ptr(), 1.0, e, 0, 0.1, S, N, hid, A, ldp, None, st)
+    bound = 4.0 * P * S * N / 8e12 * 1e6
+    print("S=%d N=%d hid=%d E=%d: actor weights %.2f GB, streamed once at 8 TB/s: %.0f us" % (S, N, hid, E, 4.0 * P * S * N / 1e9, bound))
+    for form in (1, 0):
+        L.rcmarl_wide_set_f16_mode(form)
+        t = timeit(mx, iters=10, warm=3)
+        print("matrix core, %-28s %9.1f us  = %5.2f x the bound" % ("two-piece f16 operands" if form else "fp32 MFMA (exact form)", t, t / bound))
+    L.rcmarl_wide_set_f16_mode(-1)
+    t = timeit(plain, iters=3, warm=1)
+    print("plain, %d single-state launches      %9.1f us  = %5.2f x the bound  (%.1f us per launch)" % (E, t, t / bound, t / E))
+
+
 if __name__ == "__main__":
     L = capi.CLib(os.environ["RCMARL_KBENCH_LIB"]) if os.environ.get("RCMARL_KBENCH_LIB") else capi.load()     # (variant builds)
     what = sys.argv[1] if len(sys.argv) > 1 else "gemm"
     print("== %s  RCMARL_GEMM=%s RCMARL_K1=%s" % (what, os.environ.get("RCMARL_GEMM"), os.environ.get("RCMARL_K1")))
-    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk}[what](L)
+    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk, "rollout_wide": rollout_wide}[what](L)
