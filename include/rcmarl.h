@@ -395,6 +395,14 @@ int rcmarl_wide_rows_per_chunk(void);    /* `losspart` holds ceil(B / this) floa
 /* out[s][n][b] = a2[:,b] . W3 + b3, or r_applied + gamma * that (TD target, :114-115) */
 int rcmarl_wide_head_value(const float* a2, const float* theta, const float* r_applied, float gamma, float* out, int S,
                            int N, int B, int in_dim, int hid, int ldp, int ldb, void* stream);
+/* Team-average TD error of an instance whose critic AND team-reward net are wide (agents/resilient_CAC_agents.py:95-98), rows 0..B of
+ * every (seed, agent): delta = v_tr + gamma * V(ns) - V(s), the statement of rcmarl_td_error.  Each of the three values is either a
+ * finished head output [S][N][ldb] (parts == 0; its theta may be NULL) or the value parts [S][N][parts][ldb] that rcmarl_pk_forward2
+ * left (parts = rcmarl_pk_parts(hid)): summed in rcmarl_pk_head's order and given b3 of theta_tr / theta_c here, so that pass needs no
+ * head launch.  Bit-identical to the three heads followed by rcmarl_td_error. */
+int rcmarl_wide_td_error(const float* tr_val, int tr_parts, const float* theta_tr, int tr_in_dim, int tr_hid, int tr_ldp,
+                         const float* next_val, int next_parts, const float* cur_val, int cur_parts, const float* theta_c,
+                         int c_in_dim, int c_hid, int c_ldp, float gamma, float* delta, int S, int N, int B, int ldb, void* stream);
 /* MSE head of fit() (:118): dz3 = 2 (V - y) / B; a2 is OVERWRITTEN by dz2 = W3 dz3 lrelu'(a2); grads gets gW3, gb3, gb2;
  * losspart the chunk sums of (V - y)^2 */
 int rcmarl_wide_head_fit(float* a2, const float* theta, const float* y, float* dz3, float* grads, float* losspart, int S,

@@ -175,6 +175,10 @@ SIGNATURES = {
     # a2, theta, r_applied, gamma, out, S, N, B, in_dim, hid, ldp, ldb, stream
     "rcmarl_wide_head_value": [c_f32p, c_f32p, c_f32p, c_float, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                c_stream],
+    # tr_val, tr_parts, theta_tr, tr_in_dim, tr_hid, tr_ldp, next_val, next_parts, cur_val, cur_parts, theta_c, c_in_dim, c_hid, c_ldp,
+    # gamma, delta, S, N, B, ldb, stream
+    "rcmarl_wide_td_error": [c_f32p, c_int, c_f32p, c_int, c_int, c_int, c_f32p, c_int, c_f32p, c_int, c_f32p, c_int, c_int, c_int,
+                             c_float, c_f32p, c_int, c_int, c_int, c_int, c_stream],
     # a2, theta, y, dz3, grads, losspart, S, N, B, in_dim, hid, ldp, ldb, stream
     "rcmarl_wide_head_fit": [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_int, c_stream],

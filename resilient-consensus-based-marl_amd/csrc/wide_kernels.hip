@@ -451,6 +451,31 @@ __global__ __launch_bounds__(256) void k_whead_value(const float* __restrict__ a
   out[o] = r_applied ? r_applied[o] + gamma * v : v;
 }
 
+// One value of the actor phase as rcmarl_wide_td_error reads it: parts == 0: the finished head output val[z][ldb]; parts > 0: the value
+// parts val[z][parts][ldb] of a packed-operand pass (rcmarl_pk_forward2), summed in k_pk_head's order, then + b3 = th[z * ldp + o_b3].
+struct WTdIn {
+  const float* val; int parts; const float* th; int ldp, o_b3;
+};
+
+__device__ static inline float w_td_value(const WTdIn& in, long z, int b, int ldb) {
+  if (in.parts == 0) return in.val[z * ldb + b];
+  float v = 0.f;
+  for (int t = 0; t < in.parts; ++t) v += in.val[(z * in.parts + t) * ldb + b];
+  v += in.th[z * in.ldp + in.o_b3];
+  return v;
+}
+
+// delta = v_tr + gamma * V(ns) - V(s) on rows 0..B of every (seed, agent): rcmarl_td_error's statement (multiply, then add, then
+// subtract; the library is built without contraction) behind the three heads' own sums     (agents/resilient_CAC_agents.py:95-98)
+__global__ __launch_bounds__(128) void k_wtd_error(WTdIn tr, WTdIn nxt, WTdIn cur, float gamma, float* __restrict__ delta, int B,
+                                                   int ldb) {
+  const long z = blockIdx.y;
+  const int b = blockIdx.x * 128 + threadIdx.x;
+  if (b >= B) return;
+  const float v_tr = w_td_value(tr, z, b, ldb), v_next = w_td_value(nxt, z, b, ldb), v_cur = w_td_value(cur, z, b, ldb);
+  delta[z * ldb + b] = v_tr + gamma * v_next - v_cur;
+}
+
 // MSE head, column half: diff = V - y, dz3 = 2 diff / B, loss partial of this chunk
 __global__ __launch_bounds__(256) void k_whead_fit_cols(const float* __restrict__ a2, const float* __restrict__ theta,
                                                         const float* __restrict__ y, float* __restrict__ dz3,
@@ -841,6 +866,27 @@ RCMARL_EXPORT int rcmarl_wide_head_value(const float* a2, const float* theta, co
   if (!a2 || !theta || !out || !w_dims_ok(S, N, B, in_dim, hid, ldp, ldb)) return RCMARL_ERR_ARG;
   const dim3 grid(rc_ceil_div(B, WROWS), N, S), block(256);
   RCMARL_LAUNCH(k_whead_value, grid, block, 0, stream, a2, theta, r_applied, gamma, out, N, B, in_dim, hid, ldp, ldb);
+  return rcmarl_check_launch();
+}
+
+// The team-average TD error of an instance whose critic AND team-reward net are wide, in one pass over the last rows:
+// delta[s][n][b] = v_tr + gamma * V(ns) - V(s), b < B.  Each of the three values is either a finished head output [S][N][ldb]
+// (parts == 0; theta may then be NULL) or the value parts [S][N][parts][ldb] a packed-operand pass left (parts > 0: summed and
+// given b3 here, which saves that pass its head launch).  Bit-identical to the heads followed by rcmarl_td_error.
+RCMARL_EXPORT int rcmarl_wide_td_error(const float* tr_val, int tr_parts, const float* theta_tr, int tr_in_dim, int tr_hid, int tr_ldp,
+                                       const float* next_val, int next_parts, const float* cur_val, int cur_parts,
+                                       const float* theta_c, int c_in_dim, int c_hid, int c_ldp, float gamma, float* delta, int S,
+                                       int N, int B, int ldb, void* stream) {
+  if (!tr_val || !next_val || !cur_val || !delta || S <= 0 || N <= 0 || B <= 0 || ldb < B || tr_parts < 0 || next_parts < 0 ||
+      cur_parts < 0)
+    return RCMARL_ERR_ARG;
+  if (tr_parts > 0 && (!theta_tr || tr_in_dim <= 0 || tr_hid <= 0 || tr_ldp < make_geom(tr_in_dim, tr_hid, 1).P)) return RCMARL_ERR_ARG;
+  if ((next_parts > 0 || cur_parts > 0) && (!theta_c || c_in_dim <= 0 || c_hid <= 0 || c_ldp < make_geom(c_in_dim, c_hid, 1).P))
+    return RCMARL_ERR_ARG;
+  const int o_tr = tr_parts > 0 ? make_geom(tr_in_dim, tr_hid, 1).o_b3 : 0, o_c = (next_parts > 0 || cur_parts > 0) ? make_geom(c_in_dim, c_hid, 1).o_b3 : 0;
+  const WTdIn tr{tr_val, tr_parts, theta_tr, tr_ldp, o_tr}, nxt{next_val, next_parts, theta_c, c_ldp, o_c},
+      cur{cur_val, cur_parts, theta_c, c_ldp, o_c};
+  RCMARL_LAUNCH(k_wtd_error, dim3(rc_ceil_div(B, 128), S * N), dim3(128), 0, stream, tr, nxt, cur, gamma, delta, B, ldb);
   return rcmarl_check_launch();
 }
 

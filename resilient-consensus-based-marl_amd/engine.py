@@ -65,7 +65,7 @@ class EngineConfig:
     def __init__(self, n_agents, agent_label, in_nodes, H=0, gamma=0.9, slow_lr=0.002, fast_lr=0.01, n_actions=5,
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
-                 local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID):
+                 local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -82,6 +82,9 @@ class EngineConfig:
         # hidden width of the actors: any other width than the reference's 20 takes the wide-actor kernels (rollout:
         # csrc/rollout.hip, Adam step: the dense GEMMs of csrc/wide_kernels.hip with an Adam epilogue)
         self.actor_hid = int(actor_hid)
+        # hidden width of the team-reward nets: like the critic's, any other width than 20 runs the dense-GEMM path; the two widths
+        # are independent of each other
+        self.tr_hid = int(tr_hid)
         assert len(self.agent_label) == self.n_agents and len(self.in_nodes) == self.n_agents
         if np.ndim(H) == 0:
             self.H_per_agent = [int(H)] * self.n_agents
@@ -112,6 +115,8 @@ class EngineConfig:
             raise ValueError("critic_hid must be positive")
         if self.actor_hid < 1:
             raise ValueError("actor_hid must be positive")
+        if self.tr_hid < 1:
+            raise ValueError("tr_hid must be positive")
         if self.actor_hid != HID:
             if any(lab != COOP for lab in self.agent_label):
                 raise ValueError("a wide actor (actor_hid = %d) needs an all-cooperative team: the Greedy / Malicious / Faulty agents' "
@@ -122,6 +127,9 @@ class EngineConfig:
         if not self.regular and self.critic_hid != HID:
             raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit critic: the wide head's gather / "
                              "GEMM / select chain is sized by one d (critic_hid = %d)" % self.critic_hid)
+        if not self.regular and self.tr_hid != HID:
+            raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit team-reward net: the wide head's "
+                             "gather / GEMM / select chain is sized by one d (tr_hid = %d)" % self.tr_hid)
 
     @property
     def d(self):
@@ -156,9 +164,9 @@ class RPBCACEngine:
         S, N = c.n_seeds, c.n_agents
         self.S, self.N = S, N
         self.in_c, self.in_r = N * c.n_states, N * (c.n_states + 1)
-        self.hid = {"actor": c.actor_hid, "critic": c.critic_hid, "tr": HID}
+        self.hid = {"actor": c.actor_hid, "critic": c.critic_hid, "tr": c.tr_hid}
         self.P = {"actor": net_numel(self.in_c, c.n_actions, c.actor_hid), "critic": net_numel(self.in_c, 1, c.critic_hid),
-                  "tr": net_numel(self.in_r, 1)}
+                  "tr": net_numel(self.in_r, 1, c.tr_hid)}
         self.in_dim = {"actor": self.in_c, "critic": self.in_c, "tr": self.in_r}
         self.out_dim = {"actor": c.n_actions, "critic": 1, "tr": 1}
         self.in_dim_x = {"s": self.in_c, "ns": self.in_c, "sa": self.in_r}      # width of each replay tensor
@@ -299,14 +307,18 @@ class RPBCACEngine:
             self.sync()
             self._alloc_row_buffers(max(int(need), self.cap + self.n_last, int(1.5 * self.cap)))
 
-    # ---- wide critic (hid != 20): dense-GEMM path, csrc/wide_kernels.hip ---------------------
+    # ---- wide critic / team-reward net (hid != 20): dense-GEMM path, csrc/wide_kernels.hip ---------------------
     def _init_wide(self):
         """Scratch of the dense-GEMM path: layer-1/2 activations and dz1 of one network family, the head's
-        gradient records and the neighbour-estimate matrix of the consensus step."""
-        self.wide = self.hid["critic"] != HID
+        gradient records and the neighbour-estimate matrix of the consensus step.  ONE set serves both critic-family nets (their
+        phases run one after the other on one stream), sized by the wider of the wide ones: every kernel takes the buffers by
+        pointer and strides them by its own hid, so the narrower net uses a prefix."""
+        self.wide_nets = [k for k in ("critic", "tr") if self.hid[k] != HID]
+        self.wide = bool(self.wide_nets)              # some critic-family net is wide (scratch, graph capture, side streams)
+        self.critic_wide = self.hid["critic"] != HID
         if not self.wide:
             return self._init_wide_actor()
-        S, N, L, hid, d = self.S, self.N, self.lib, self.hid["critic"], self.cfg.d
+        S, N, L, hid, d = self.S, self.N, self.lib, max(self.hid[k] for k in self.wide_nets), self.cfg.d
         f32 = dict(dtype=torch.float32, device=self.dev)
         assert self.ldb >= self.EP_pad()
         self.w_a1, self.w_a2, self.w_dz1 = (torch.zeros(S, N * hid, self.ldb, **f32) for _ in range(3))
@@ -349,11 +361,12 @@ class RPBCACEngine:
         self.pk = None
         if self._pk_range_fallback:
             return
-        if not (self.wide and getattr(self, "lat_enabled", False)) or self.hid["critic"] % 128:
+        nets = [k for k in self.wide_nets if self.hid[k] % 128 == 0]         # the nets this path serves
+        if not (nets and getattr(self, "lat_enabled", False)):
             return
         if os.environ.get("RCMARL_WIDE_PK", "1") in ("0", "false"):
             return
-        S, N, hid = self.S, self.N, self.hid["critic"]
+        S, N, hid = self.S, self.N, max(self.hid[k] for k in nets)           # transient operands: sized by the wider net
         Z, Bp, JT, JK = S * N, (self.cap + 255) // 256 * 256, hid // 128, hid // 32
 
         class _Pk:
@@ -361,10 +374,16 @@ class RPBCACEngine:
         pk = _Pk()
         u8 = lambda n: torch.zeros(int(n), dtype=torch.uint8, device=self.dev)
         f32 = dict(dtype=torch.float32, device=self.dev)
-        pk.Bp, pk.bk_rt, pk.kb_kt = Bp, Bp // 128, Bp // 32
-        pk.a1_bk = {"net": u8(Z * pk.bk_rt * JK * 2 * LT.PK_BLOCK), "scratch": u8(Z * pk.bk_rt * JK * 2 * LT.PK_BLOCK)}
-        pk.a1_kb = u8(Z * JT * pk.kb_kt * 2 * LT.PK_BLOCK)
-        pk.s1 = torch.zeros(Z * hid, Bp // 32, dtype=torch.int32, device=self.dev)
+        pk.Bp, pk.bk_rt, pk.kb_kt, pk.nets = Bp, Bp // 128, Bp // 32, tuple(nets)
+        # the image a fit / the consensus step leaves behind is what survives an epoch: ONE PER NET (both orientations and the sign
+        # bits), so that the other net's phases never write into it; value passes of either net share "scratch"
+        pk.a1_bk = {"scratch": u8(Z * pk.bk_rt * JK * 2 * LT.PK_BLOCK)}
+        pk.a1_kb, pk.s1 = {}, {}
+        for k in nets:
+            h = self.hid[k]
+            pk.a1_bk[k] = u8(Z * pk.bk_rt * (h // 32) * 2 * LT.PK_BLOCK)
+            pk.a1_kb[k] = u8(Z * (h // 128) * pk.kb_kt * 2 * LT.PK_BLOCK)
+            pk.s1[k] = torch.zeros(Z * h, Bp // 32, dtype=torch.int32, device=self.dev)
         pk.w2t, pk.w2w3 = u8(Z * JT * JK * 2 * LT.PK_BLOCK), u8(Z * JT * JK * 2 * LT.PK_BLOCK)
         pk.rs = torch.zeros(Z, hid, **f32)
         pk.mask_bj, pk.mask_jb = u8(Z * pk.bk_rt * JK * LT.PK_BLOCK), u8(Z * JT * pk.kb_kt * LT.PK_BLOCK)
@@ -377,27 +396,27 @@ class RPBCACEngine:
 
     def _pk_ok(self, net, xkey, B, row0=0):
         """does this pass of a wide net run on the packed-operand path?  (lattice layer 1 on these rows, both operand forms f16)"""
-        return (self.pk is not None and self.hid[net] != HID and self._lattice_ok(xkey, B, row0)
+        return (self.pk is not None and net in self.pk.nets and self._lattice_ok(xkey, B, row0)
                 and self.lib.rcmarl_pk_supported(self.hid[net]) == 1 and self.lib.rcmarl_wide_f16_mode() == 1)
 
     def _wide_forward_pk(self, xkey, theta, net, B, which, fit=False, want_a2=False, skip_layer1=False, wp_fresh=False):
-        """layers 1 and 2 of a wide net on packed operands.  which: 'net' (the image a fit / the consensus step leaves behind) or
-        'scratch' (value passes).  fit: also a1_kb, s1, the layer-2 masks.  Always leaves the head's value parts in pk.vpart;
+        """layers 1 and 2 of a wide net on packed operands.  which: 'net' (this net's own image, the one a fit / the consensus step
+        leaves behind) or 'scratch' (value passes).  fit: also a1_kb, s1, the layer-2 masks.  Always leaves the head's value parts in pk.vpart;
         want_a2: the fp32 layer-2 activations in self.w_a2 (phi of the estimate consensus)."""
         L, S, N, hid, pk, st = self.lib, self.S, self.N, self.hid[net], self.pk, self.stream
         in_dim, ldp = self.in_dim[net], self.ldp[net]
         g, wp = self.lat_geom[xkey], self.lat_wp_f[xkey]
-        a1_bk = pk.a1_bk[which]
+        full = which == "net"                  # the cached image always carries both orientations and the sign bits
+        a1_bk, a1_kb, s1 = pk.a1_bk[net if full else which], pk.a1_kb[net], pk.s1[net]
         if want_a2:
             self.a2_cached = False
-        full = which == "net"                  # the cached image always carries both orientations and the sign bits
         if not skip_layer1:
             if not wp_fresh:
                 L.rcmarl_w1_split(theta.data_ptr(), self.lat_alpha[xkey].data_ptr(), wp.data_ptr(), S, N, in_dim, hid, ldp, g.wp[0],
                                   g.wp[1], st)
             L.rcmarl_layer1_forward_lattice_pk(self.lat_kp[xkey].data_ptr(), g.kp[0], g.kp[1], wp.data_ptr(), g.wp[0], g.wp[1],
-                                               theta.data_ptr(), a1_bk.data_ptr(), pk.bk_rt, pk.a1_kb.data_ptr() if full else None,
-                                               pk.kb_kt, pk.s1.data_ptr() if full else None, pk.Bp // 32, pk.ovf.data_ptr(), S, N, B,
+                                               theta.data_ptr(), a1_bk.data_ptr(), pk.bk_rt, a1_kb.data_ptr() if full else None,
+                                               pk.kb_kt, s1.data_ptr() if full else None, pk.Bp // 32, pk.ovf.data_ptr(), S, N, B,
                                                in_dim, hid, ldp, st)
         L.rcmarl_pk_pack_w2(theta.data_ptr(), pk.w2t.data_ptr(), pk.w2w3.data_ptr(), pk.rs.data_ptr(), pk.ovf.data_ptr(), S, N, in_dim,
                             hid, ldp, st)
@@ -418,11 +437,11 @@ class RPBCACEngine:
                                   wp_fresh=wp_fresh)
             L.rcmarl_pk_head(pk.vpart.data_ptr(), msg.data_ptr(), y.data_ptr(), 0.0, 2, self.w_dz3.data_ptr(), pk.dzv.data_ptr(),
                              self.w_losspart.data_ptr(), S, N, B, in_dim, hid, ldp, ldb, st)
-            L.rcmarl_pk_backward_data(pk.mask_bj.data_ptr(), pk.bk_rt, pk.w2w3.data_ptr(), pk.rs.data_ptr(), pk.s1.data_ptr(),
+            L.rcmarl_pk_backward_data(pk.mask_bj.data_ptr(), pk.bk_rt, pk.w2w3.data_ptr(), pk.rs.data_ptr(), pk.s1[net].data_ptr(),
                                       pk.Bp // 32, self.w_dz3.data_ptr(), dzp.data_ptr(), g.dzp[0], g.dzp[1], pk.gb1part.data_ptr(),
                                       pk.ovf.data_ptr(), S, N, B, hid, ldb, st)
             # every gradient comes from the pre-step weights: the W2 step reads W3, the small step updates it afterwards
-            L.rcmarl_pk_backward_w2(pk.a1_kb.data_ptr(), pk.kb_kt, pk.mask_jb.data_ptr(), pk.kb_kt, pk.dzv.data_ptr(), msg.data_ptr(),
+            L.rcmarl_pk_backward_w2(pk.a1_kb[net].data_ptr(), pk.kb_kt, pk.mask_jb.data_ptr(), pk.kb_kt, pk.dzv.data_ptr(), msg.data_ptr(),
                                     mask.data_ptr(), pk.gw3part.data_ptr(), pk.q.data_ptr(), S, N, B, in_dim, hid, ldp, lr, st)
             L.rcmarl_layer1_backward_sgd_lattice(self.lat_ktp[xkey].data_ptr(), g.ktp[0], g.ktp[1], dzp.data_ptr(), g.dzp[0], g.dzp[1],
                                                  self.lat_alpha[xkey].data_ptr(), msg.data_ptr(), mask.data_ptr(), S, N, B, in_dim,
@@ -563,6 +582,9 @@ class RPBCACEngine:
         if self.actor_wide:
             raise ValueError("agent sharding keeps the actors replicated on the 20-unit kernels: a wide actor (actor_hid = %d) "
                              "is not sharded" % self.cfg.actor_hid)
+        if self.hid["tr"] != HID:
+            raise ValueError("agent sharding keeps the team-reward net on the 20-unit kernels: a wide one (tr_hid = %d) shares the "
+                             "wide critic's scratch, which the agent window slices by the critic's width -- not sharded" % self.cfg.tr_hid)
         if comm is None and world is None:
             comm = TorchComm(group)
         if comm is not None:
@@ -570,7 +592,7 @@ class RPBCACEngine:
         if world == 1 and not force:
             self.shard = None
             return self
-        if self.S != 1 or not self.wide:
+        if self.S != 1 or not self.critic_wide:
             raise ValueError("agent sharding is for ONE instance (n_seeds == 1) with a wide critic; independent seeds shard "
                              "over ranks without any exchange (parallel.shard_seeds)")
         if self.N % world:
@@ -899,8 +921,8 @@ class RPBCACEngine:
             sd[k] = getattr(self, k).detach().cpu()
         if hasattr(self, "adv"):
             sd["adv"] = self.adv.state_dict()
-        sd["shape"] = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "actor_hid": c.actor_hid, "buffer_size": c.buffer_size, "n_ep_fixed": c.n_ep_fixed,
-                       "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
+        sd["shape"] = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "actor_hid": c.actor_hid, "tr_hid": c.tr_hid, "buffer_size": c.buffer_size,
+                       "n_ep_fixed": c.n_ep_fixed, "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
         if self.np_rngs is not None:          # plain tensors / numbers only, so the file loads with weights_only=True
             sd["np_rngs"] = []
             for r in self.np_rngs:
@@ -915,10 +937,11 @@ class RPBCACEngine:
             raise ValueError("checkpoint does not match this engine (format/S/N/agent labels)")
         if [list(map(int, r)) for r in sd["in_nodes"]] != c.in_nodes:
             raise ValueError("checkpoint was written for a different communication graph")
-        mine = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "actor_hid": c.actor_hid, "buffer_size": c.buffer_size,
+        mine = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "actor_hid": c.actor_hid, "tr_hid": c.tr_hid, "buffer_size": c.buffer_size,
                 "n_ep_fixed": c.n_ep_fixed, "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
         theirs = dict(sd.get("shape", mine))
         theirs.setdefault("actor_hid", HID)              # files written before actors could be wide
+        theirs.setdefault("tr_hid", HID)                 # ... before team-reward nets could be
         diff = {k: (theirs.get(k), v) for k, v in mine.items() if theirs.get(k) != v}
         if "H" in diff and self._H_list(theirs.get("H")) == c.H_per_agent:      # the same per-agent H, written the other way
             del diff["H"]
@@ -999,7 +1022,7 @@ class RPBCACEngine:
         else:
             self._reset(None if c.randomize_state else np.broadcast_to(np.asarray(self.initial_state), (S, N, 2)))
         # expected returns at the start state (train_agents.py:60-62)
-        if self.wide:
+        if self.critic_wide:
             with self._agent_window():
                 self._value_wide(None, self.theta["critic"], "critic", self.w_v, 1, x=(self.xs[self.cur].data_ptr(), 2 * N, 1, 2 * N))
             if self.shard is not None:
@@ -1058,7 +1081,7 @@ class RPBCACEngine:
         L.rcmarl_env_reset_episodes(self._p(pin), self.seeds_dev.data_ptr(), c.nrow, c.ncol, self.scale.data_ptr(),
                                     self.episode, self.posT[0].data_ptr(), self.xsT[0].data_ptr(), self.retT.data_ptr(),
                                     S, N, n_eps, EP, self.stream)
-        if self.wide:      # start states are episode-minor xsT[S][2N][EP]: a feature-major layer-1 input
+        if self.critic_wide:      # start states are episode-minor xsT[S][2N][EP]: a feature-major layer-1 input
             with self._agent_window():
                 self._value_wide(None, self.theta["critic"], "critic", self.w_v, n_eps, x=(self.xsT[0].data_ptr(), 2 * N * EP, 0, EP))
             if self.shard is not None:
@@ -1291,7 +1314,7 @@ class RPBCACEngine:
         """wide critic: may the values of the next states come from the fp32 layer-2 activations the consensus step's forward pass
         left in w_a2?  (live hidden layers unchanged since, rows are whole episodes of ours)"""
         ep = self.cfg.max_ep_len
-        return (self.td_shortcut and self.a2_cached and self.wide and self.rows_episode_aligned and ep >= 2
+        return (self.td_shortcut and self.a2_cached and self.critic_wide and self.rows_episode_aligned and ep >= 2
                 and row0 % ep == 0 and nrows % ep == 0)
 
     def _value_cached_wide(self, out, row0, nrows):
@@ -1423,7 +1446,8 @@ class RPBCACEngine:
         if join is not None:
             torch.cuda.current_stream(self.dev).wait_event(join)
         t0 = self._timed("phase1", t0)
-        # II) resilient consensus (cooperative agents)
+        # II) resilient consensus (cooperative agents).  (A wide team-reward net's forward pass overwrites the shared w_a2 and
+        # clears a2_cached: beside it a wide critic's TD target takes a forward pass of its own, not the cached activations.)
         self._consensus("critic", "s", B)
         self._consensus("tr", "sa", B)
         return self._timed("phase2", t0)
@@ -1540,25 +1564,11 @@ class RPBCACEngine:
         c, L, S, N = self.cfg, self.lib, self.S, self.N
         nl = self.n_last
         row0 = B - nl
-        # team-average TD error (agents/resilient_CAC_agents.py:95-98): the last consensus step left the layer-1
-        # activations of the live TR net and critic on every row, so no forward GEMM is needed here
-        if self._cached_rows_ok("tr", row0, nl):
-            self._value_cached("tr", self.ybuf["v_tr"], row0, nl)
+        # team-average TD error (agents/resilient_CAC_agents.py:95-98)
+        if self.critic_wide and self.hid["tr"] != HID:
+            self._td_error_both_wide(row0, nl)
         else:
-            self._value("sa", self.theta["tr"], "tr", self.ybuf["v_tr"], nl, row0, gather=True)
-        if self._cached_rows_ok("critic", row0, nl):
-            self._value_next_cached(self.ybuf["v_next"], row0, nl, None, self.ybuf["delta"])
-            self._value_cached("critic", self.ybuf["v_cur"], row0, nl)
-        elif self._a2_rows_ok(row0, nl):
-            # wide critic: both values from the fp32 layer-2 activations the last consensus step left behind (V(s) first: the forward
-            # pass over the episodes' last next-state rows inside _value_next_cached_wide re-uses that buffer)
-            self._value_cached_wide(self.ybuf["v_cur"], row0, nl)
-            self._value_next_cached_wide(self.ybuf["v_next"], row0, nl, None, self.ybuf["delta"], gather=True)
-        else:
-            self._value("ns", self.theta["critic"], "critic", self.ybuf["v_next"], nl, row0, gather=True)
-            self._value("s", self.theta["critic"], "critic", self.ybuf["v_cur"], nl, row0, gather=True)
-        L.rcmarl_td_error(self.ybuf["v_tr"].data_ptr(), self.ybuf["v_next"].data_ptr(), self.ybuf["v_cur"].data_ptr(),
-                          c.gamma, self.ybuf["delta"].data_ptr(), S * N * self.ldb, self.stream)
+            self._td_error(row0, nl)
         aptr, astride = self._x("a", row0)
         L.rcmarl_gather_agent_major(aptr, astride, None, None, self.ybuf["act_t"].data_ptr(), S, N, nl, self.ldb, self.stream)
         self.adam_t += 1
@@ -1578,6 +1588,43 @@ class RPBCACEngine:
         L.rcmarl_layer1_backward_adam(sptr, sstride, self.a1t.data_ptr(), self.theta["actor"].data_ptr(),
                                       self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.coop.data_ptr(), S, N, nl,
                                       self.in_c, HID, self.ldp["actor"], self.ldb, alpha, omb1, omb2, epsf, self.stream)
+
+    def _td_error(self, row0, nl):
+        """delta = v_tr + gamma V(ns) - V(s) on the last nl rows, then rcmarl_td_error.  20-unit nets: the last consensus step left
+        the layer-1 activations of the live net on every row, so no forward GEMM is needed for them; a wide net takes a forward pass
+        of its own (a wide critic without a wide team-reward net: its cached layer-2 activations where they are valid)."""
+        c, L, S, N = self.cfg, self.lib, self.S, self.N
+        if self._cached_rows_ok("tr", row0, nl):
+            self._value_cached("tr", self.ybuf["v_tr"], row0, nl)
+        else:
+            self._value("sa", self.theta["tr"], "tr", self.ybuf["v_tr"], nl, row0, gather=True)
+        if self._cached_rows_ok("critic", row0, nl):
+            self._value_next_cached(self.ybuf["v_next"], row0, nl, None, self.ybuf["delta"])
+            self._value_cached("critic", self.ybuf["v_cur"], row0, nl)
+        elif self._a2_rows_ok(row0, nl):
+            # wide critic: both values from the fp32 layer-2 activations the last consensus step left behind (V(s) first: the forward
+            # pass over the episodes' last next-state rows inside _value_next_cached_wide re-uses that buffer)
+            self._value_cached_wide(self.ybuf["v_cur"], row0, nl)
+            self._value_next_cached_wide(self.ybuf["v_next"], row0, nl, None, self.ybuf["delta"], gather=True)
+        else:
+            self._value("ns", self.theta["critic"], "critic", self.ybuf["v_next"], nl, row0, gather=True)
+            self._value("s", self.theta["critic"], "critic", self.ybuf["v_cur"], nl, row0, gather=True)
+        L.rcmarl_td_error(self.ybuf["v_tr"].data_ptr(), self.ybuf["v_next"].data_ptr(), self.ybuf["v_cur"].data_ptr(),
+                          c.gamma, self.ybuf["delta"].data_ptr(), S * N * self.ldb, self.stream)
+
+    def _td_error_both_wide(self, row0, nl):
+        """_td_error of an instance whose critic and team-reward net are both wide (never agent-sharded): three full value passes on
+        the last nl rows, then rcmarl_wide_td_error over those rows.  The passes keep their head launches: in steady state the last
+        rows are not the whole buffer, so they run on the dense path, whose head reads a2 itself (the entry point's value-parts
+        form serves a caller whose passes ran on packed operands; the engine hands it finished head outputs, parts = 0)."""
+        c, L, S, N, yb = self.cfg, self.lib, self.S, self.N, self.ybuf
+        self.a2_cached = False                 # (the team-reward net's consensus step ran last and overwrote w_a2; so do these passes)
+        self._value_wide("sa", self.theta["tr"], "tr", yb["v_tr"], nl, row0)
+        self._value_wide("ns", self.theta["critic"], "critic", yb["v_next"], nl, row0)
+        self._value_wide("s", self.theta["critic"], "critic", yb["v_cur"], nl, row0)
+        L.rcmarl_wide_td_error(yb["v_tr"].data_ptr(), 0, None, self.in_r, self.hid["tr"], self.ldp["tr"], yb["v_next"].data_ptr(), 0,
+                               yb["v_cur"].data_ptr(), 0, None, self.in_c, self.hid["critic"], self.ldp["critic"], c.gamma,
+                               yb["delta"].data_ptr(), S, N, nl, self.ldb, self.stream)
 
     def _actor_step_wide(self, nl, row0, alpha, omb1, omb2, epsf):
         """The Adam step of _actor_update for a wide actor: every layer a dense GEMM per agent (csrc/wide_kernels.hip), the Adam
@@ -1714,7 +1761,7 @@ class RPBCACEngine:
                           "in fp32", RuntimeWarning)
             self._pk_range_fallback = True
             self.pk = None
-            self.a1_cached["critic"] = self.a2_cached = False
+            self.a1_cached["critic"] = self.a1_cached["tr"] = self.a2_cached = False
 
     def _warn_if_diverged(self):
         """The reference's plain-SGD local fits diverge to NaN when fast_lr is too large for the input width

@@ -52,6 +52,7 @@ class AdversaryPath:
         self.calls = [0] * eng.S                       # ShuffleStream.calls per seed
         self.base_dev, self._draw_bufs, self.last_draw = None, {}, 0
         self.adam_t = 0                                # Adam steps every adversary's actor has taken
+        self._mb = {}                                  # mini-batch scratch of the wide fits, per width (critic and team-reward net may differ)
         f32 = dict(dtype=torch.float32, device=dev)
         for k in ("r_own", "y_l", "y_adv", "delta_adv", "v_next_adv", "v_cur_adv"):
             eng.ybuf[k] = torch.zeros(eng.S, eng.N, eng.ldb, **f32)
@@ -106,35 +107,37 @@ class AdversaryPath:
         self.calls = [c + draws for c in self.calls]
 
     # -- Keras fit(batch_size=32, epochs=10) of a critic-family network, any width ----------------------------
-    def _fit_critic_family(self, theta, agents_t, agents, y, perm, B, loss_out):
+    def _fit_critic_family(self, theta, agents_t, agents, y, perm, B, loss_out, net="critic", xkey="s", flag_key=None):
         """theta [S][N][ldp] (fitted in place, rows `agents`), targets y [S][N][ldb], perm int32 [S][len(agents)][epochs][B]
-        (agents/adversarial_CAC_agents.py:131-135,146-152,237-241)."""
+        (agents/adversarial_CAC_agents.py:131-135,146-152,237-241).  net / xkey: the family's geometry and replay tensor
+        ("critic" on "s", "tr" on "sa")."""
         e, L = self.e, self.e.lib
-        hid = e.hid["critic"]
-        xptr, xstride = e._x("s")
+        hid = e.hid[net]
+        xptr, xstride = e._x(xkey)
         if hid == HID:
             L.rcmarl_minibatch_fit(xptr, xstride, theta.data_ptr(), agents_t.data_ptr(), len(agents), y.data_ptr(),
-                                   perm.data_ptr(), e.S, e.N, B, e.in_c, HID, e.ldp["critic"], e.ldb, FIT_BATCH, FIT_EPOCHS,
+                                   perm.data_ptr(), e.S, e.N, B, e.in_dim[net], HID, e.ldp[net], e.ldb, FIT_BATCH, FIT_EPOCHS,
                                    e.cfg.fast_lr, None if loss_out is None else loss_out.data_ptr(),
-                                   e.ovf_flags(("adv", theta.data_ptr()), e.S * len(agents)).data_ptr(), e.stream)
+                                   e.ovf_flags(("adv", theta.data_ptr() if flag_key is None else flag_key), e.S * len(agents)).data_ptr(),
+                                   e.stream)
             return
         # wide critic: one SGD step = forward L1, forward L2, head fit (dz3, dz2 in place, gW3/gb3/gb2), backward-data L2
         # (-> dz1), bias grad, backward-SGD W2, backward-SGD W1, small SGD -- every gradient from the pre-step weights, as
         # RPBCACEngine._local_fit_wide does for a full batch; here on (seed, agent) = (1, 1) views and 32 permuted rows
-        in_dim, ldp, lr, st = e.in_c, e.ldp["critic"], e.cfg.fast_lr, e.stream
+        in_dim, ldp, lr, st = e.in_dim[net], e.ldp[net], e.cfg.fast_lr, e.stream
         o_b1 = in_dim * hid
         o_W2 = o_b1 + hid
         o_b2 = o_W2 + hid * hid
         ldm = 64                                        # row stride of the mini-batch scratch (>= FIT_BATCH, % 64 == 0)
-        if getattr(self, "_mb", None) is None or self._mb["hid"] != hid:
+        if hid not in self._mb:
             f32 = dict(dtype=torch.float32, device=e.dev)
-            self._mb = {"hid": hid, "a1": torch.zeros(hid, ldm, **f32), "a2": torch.zeros(hid, ldm, **f32),
+            self._mb[hid] = {"a1": torch.zeros(hid, ldm, **f32), "a2": torch.zeros(hid, ldm, **f32),
                         "dz1": torch.zeros(hid, ldm, **f32), "dz3": torch.zeros(ldm, **f32),
                         "grads": torch.zeros(L.rcmarl_wide_grad_size(hid), **f32), "lp": torch.zeros(4, **f32),
                         "loss": torch.zeros(1, **f32), "one": torch.ones(1, dtype=torch.int32, device=e.dev)}
-        m = self._mb
+        m = self._mb[hid]
         a1, a2, dz1, dz3, grads, lp, one = (m[k].data_ptr() for k in ("a1", "a2", "dz1", "dz3", "grads", "lp", "one"))
-        X = e.rp["s"]
+        X = e.rp[xkey]
         for s_ in range(e.S):
             for q, ag in enumerate(agents):
                 th = theta.data_ptr() + 4 * ((s_ * e.N + ag) * ldp)
@@ -212,11 +215,8 @@ class AdversaryPath:
                 done(2)
         # transmitted TR: targets r_fit (own reward for Greedy, -r_coop for Malicious)
         with on(1):
-            xptr, xstride = e._x("sa")
-            L.rcmarl_minibatch_fit(xptr, xstride, e.theta["tr"].data_ptr(), self.fit_t.data_ptr(), len(self.fit),
-                                   e.ybuf["r_fit"].data_ptr(), perms["tr"].data_ptr(), S, N, B, e.in_r, HID, e.ldp["tr"],
-                                   e.ldb, FIT_BATCH, FIT_EPOCHS, e.cfg.fast_lr, e.loss["tr"].data_ptr(),
-                                   e.ovf_flags(("adv", "tr"), S * len(self.fit)).data_ptr(), e.stream)
+            self._fit_critic_family(e.theta["tr"], self.fit_t, self.fit, e.ybuf["r_fit"], perms["tr"], B, e.loss["tr"], net="tr",
+                                    xkey="sa", flag_key="tr")
             self._publish("tr")                        # the fitted net IS the message
             done(1)
         # transmitted critic: targets y_c = r_fit + gamma*V_theta(ns), computed from the pre-fit weights

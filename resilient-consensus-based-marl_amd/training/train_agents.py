@@ -28,11 +28,11 @@ def _truthy(v):
 def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
     n_agents = env.n_agents
     labels = list(args['agent_label'])
-    # hidden widths come from the model objects (the reference builds 20-unit networks, main.py:59-82): the critic and the
-    # actor may be wider (BASELINE configs[4]: 512 units -> dense-GEMM paths of the engine); the team-reward net stays at 20
+    # hidden widths come from the model objects (the reference builds 20-unit networks, main.py:59-82): each of the three nets may
+    # be wider (BASELINE configs[4]: 512 units -> dense-GEMM paths of the engine), independently of the other two
     widths = {attr: {int(np.shape(getattr(ag, attr).get_weights()[0])[1]) for ag in agents} for _, attr in _NETS}
-    if len(widths["actor"]) != 1 or widths["TR"] != {20} or len(widths["critic"]) != 1:
-        raise ValueError("unsupported hidden widths %r: the team-reward net must have 20 hidden units, all critics the same "
+    if len(widths["actor"]) != 1 or len(widths["TR"]) != 1 or len(widths["critic"]) != 1:
+        raise ValueError("unsupported hidden widths %r: all team-reward nets must have the same width, all critics the same "
                          "width and all actors the same width" % widths)
     # H is per agent (RPBCAC_agent(..., H=...)); the adversaries' classes carry none and never aggregate.  args['H'] may itself be
     # one int or one per agent (main.py --H)
@@ -41,7 +41,8 @@ def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
     H_coop = {h for h, lab in zip(H, labels) if lab == 'Cooperative'}
     if len(H_coop) == 1:                       # one H among the cooperative agents: the uniform-H kernels
         H = H_coop.pop()
-    cfg = EngineConfig(n_agents, labels, args['in_nodes'], critic_hid=widths["critic"].pop(), actor_hid=widths["actor"].pop(), H=H, gamma=args['gamma'],
+    cfg = EngineConfig(n_agents, labels, args['in_nodes'], critic_hid=widths["critic"].pop(), actor_hid=widths["actor"].pop(),
+                       tr_hid=widths["TR"].pop(), H=H, gamma=args['gamma'],
                        slow_lr=args['slow_lr'],
                        fast_lr=args['fast_lr'], n_actions=args['n_actions'], n_states=args['n_states'],
                        max_ep_len=args['max_ep_len'], n_ep_fixed=args['n_ep_fixed'], n_epochs=args['n_epochs'],
