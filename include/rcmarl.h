@@ -250,6 +250,18 @@ typedef struct rcmarl_mb_job {
 int rcmarl_minibatch_fit_multi(const rcmarl_mb_job* jobs, int njobs, int S, int N, int B, int hid, int ldb, int batch_size,
                                int epochs, float lr, void* stream);
 
+/* The same fits for a critic-family net of ANY hidden width (csrc/minibatch_wide.hip): fp32 operands and accumulation on the exact-f32
+ * matrix instruction, one workgroup per chain, the mini-batch activations in LDS, the parameters updated in place in `theta`.
+ * rcmarl_minibatch_fit_wide_supported: 1: this (in_dim, hid, batch_size) is served (the activations of a mini-batch fit the LDS:
+ *   every hid <= 256 with batch_size <= 32, and what the layout holds beyond); 0 otherwise.  Host-only.
+ * rcmarl_minibatch_fit_wide: njobs (1..4) independent fits in ONE launch, one workgroup per (job, seed, adversary).  jobs: the
+ *   rcmarl_mb_job array of rcmarl_minibatch_fit_multi (HOST memory, read during the call; ovf_flags unused here, may be NULL;
+ *   reserved_ ignored), hid[njobs]: hidden width per job (HOST memory).  Jobs may differ in in_dim, ldp and hid.  Bad arguments
+ *   return RCMARL_ERR_ARG before the HIP runtime is touched; an unserved shape (batch_size > 32 included) RCMARL_ERR_UNSUPPORTED. */
+int rcmarl_minibatch_fit_wide_supported(int in_dim, int hid, int batch_size);
+int rcmarl_minibatch_fit_wide(const rcmarl_mb_job* jobs, const int* hid, int njobs, int S, int N, int B, int ldb,
+                              int batch_size, int epochs, float lr, void* stream);
+
 /* X1: one whole Keras fit() of the adversaries' networks per launch (one workgroup per (seed, adversary)).
  * agents: int[n_adv] agent indices; the rows theta[s][agents[k]] are trained IN PLACE.
  * perm: int[S][n_adv][epochs][B] row permutation per epoch (Keras shuffle; NULL = natural order).

@@ -15,10 +15,16 @@ Replaces, for all seeds at once, what the reference does per adversarial agent i
 
 Every Keras ``fit`` of a 20-unit network is ONE kernel launch (csrc/minibatch_fit.hip): the whole
 sequence of mini-batch steps of one (seed, adversary) network runs inside one
-workgroup.  A critic of any other width (BASELINE configs[4]: 512 units) takes the same
-mini-batch steps through the dense per-agent GEMM entry points (rcmarl_dense_*, one step =
-the eight launches of a wide local-fit step on 32 rows): correct and slow -- a Byzantine agent
-beside a wide critic is what the algorithm is for, not a throughput case.  Keras shuffles with TensorFlow's RNG; here the permutations come from
+wavefront.  A critic or team-reward net of any other width whose mini-batch activations fit
+the LDS (rcmarl_minibatch_fit_wide_supported: widths up to 384 with mini-batches of 32 rows)
+keeps that shape: ALL such fits of a consensus epoch -- the Malicious agents' private critic,
+the transmitted team-reward net, the transmitted critic, for all seeds and adversaries -- are
+ONE rcmarl_minibatch_fit_wide launch (csrc/minibatch_wide.hip, one workgroup per chain, fp32 on
+the exact-f32 matrix instruction), beside rcmarl_minibatch_fit for a 20-unit net of the same
+engine.  Only a width the query does not serve (BASELINE configs[4]: 512 units) still takes
+the same mini-batch steps through the dense per-agent GEMM entry points (rcmarl_dense_*, one
+step = the eight launches of a wide local-fit step on 32 rows, chains one after the other in a
+Python loop): correct and slow.  Keras shuffles with TensorFlow's RNG; here the permutations come from
 a counter-based stream (csrc/shuffle.hip, generated on the device for all seeds at once; the oracle
 states the same definition), consumed in the reference's call order so that oracle and engine stay in
 lock step.
@@ -182,6 +188,8 @@ class AdversaryPath:
         S, N = e.S, e.N
         if self._multi_ok():
             return self._phase1_multi(B, perms)
+        if e.wide:
+            return self._phase1_wide(B, perms)
         # The (up to) three fits are independent networks and each is ONE latency-bound workgroup per (seed, adversary):
         # on a GPU they run side by side on three streams (forked from / joined to the current one).
         par = e.dev.type == "cuda" and not e.wide and os.environ.get("RCMARL_ADV_ASYNC", "1") not in ("0", "false")
@@ -267,6 +275,40 @@ class AdversaryPath:
         arr = (capi.MbJob * len(jobs))(*jobs)
         L.rcmarl_minibatch_fit_multi(arr, len(jobs), S, N, B, HID, e.ldb, FIT_BATCH, FIT_EPOCHS, e.cfg.fast_lr, e.stream)
         self._publish("tr")
+        self._publish("critic")
+
+    def _wide_served(self, net):
+        """this family's fits go into the one rcmarl_minibatch_fit_wide launch of the epoch: a net wider than 20 units whose
+        mini-batch activations fit the LDS (the library's own query)"""
+        e = self.e
+        return e.hid[net] != HID and e.lib.rcmarl_minibatch_fit_wide_supported(e.in_dim[net], e.hid[net], FIT_BATCH) == 1
+
+    def _phase1_wide(self, B, perms):
+        """phase I beside a wide net: every fit of the epoch whose net is wide and served -- the Malicious agents' private critic,
+        the transmitted team-reward net, the transmitted critic -- in ONE launch for all seeds and adversaries; a 20-unit net
+        beside them keeps rcmarl_minibatch_fit and an unserved width the launch-per-step loop (_fit_critic_family)."""
+        from . import capi
+        e, L = self.e, self.e.lib
+        fits = []                                      # the arguments of _fit_critic_family, in the reference's order
+        if self.mal:
+            self._local_targets(B)
+            fits.append((e.theta["critic_local"], self.mal_t, self.mal, e.ybuf["y_l"], perms["local"], B, None, "critic", "s", None))
+        fits.append((e.theta["tr"], self.fit_t, self.fit, e.ybuf["r_fit"], perms["tr"], B, e.loss["tr"], "tr", "sa", "tr"))
+        fits.append((e.theta["critic"], self.fit_t, self.fit, e.ybuf["y_c"], perms["critic"], B, e.loss["critic"], "critic", "s", None))
+        jobs, hids = [], []
+        for f in fits:
+            theta, agents_t, agents, y, perm, _, loss, net, xkey, _ = f
+            if not self._wide_served(net):
+                self._fit_critic_family(*f)
+                continue
+            xptr, xstride = e._x(xkey)
+            jobs.append(capi.MbJob(xptr, xstride, theta.data_ptr(), agents_t.data_ptr(), len(agents), e.in_dim[net], e.ldp[net], 0,
+                                   y.data_ptr(), perm.data_ptr(), None if loss is None else loss.data_ptr(), None))
+            hids.append(e.hid[net])
+        if jobs:
+            L.rcmarl_minibatch_fit_wide((capi.MbJob * len(jobs))(*jobs), (capi.c_int * len(hids))(*hids), len(jobs), e.S, e.N, B,
+                                        e.ldb, FIT_BATCH, FIT_EPOCHS, e.cfg.fast_lr, e.stream)
+        self._publish("tr")                            # the fitted nets ARE the messages
         self._publish("critic")
 
     # -- phase III ---------------------------------------------------------------------------

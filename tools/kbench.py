@@ -6,6 +6,7 @@
     python tools/kbench.py k1_ragged # consensus_params_ragged on a degree mix against one masked uniform launch per class
     python tools/kbench.py mid       # mid_fit / consensus_head / mid_value
     python tools/kbench.py rollout_wide  # wide actor: one step of 50 episodes, matrix-core kernel vs plain kernel vs the weight stream
+    python tools/kbench.py mb_wide   # adversaries beside 64-unit nets: one rcmarl_minibatch_fit_wide launch vs the eight launches per step
 """
 import os
 import sys
@@ -581,8 +582,62 @@ def rollout_wide(L, S=1, N=int(os.environ.get("RCMARL_KBENCH_N", "1024")), hid=5
     print("plain, %d single-state launches      %9.1f us  = %5.2f x the bound  (%.1f us per launch)" % (E, t, t / bound, t / E))
 
 
+def mb_wide(L, N=5, B=2000, hid=64, epochs=10, bs=32):
+    """the three chains a Malicious agent needs per consensus epoch beside 64-unit nets (private critic, team-reward net, critic:
+    10, 15 and 10 inputs), one adversary, for S seeds: ONE rcmarl_minibatch_fit_wide launch against the launch-per-step loop's eight
+    launches of one mini-batch step on a (seed, agent) = (1, 1) view (the yardstick; a library without the new entry point times
+    only that)"""
+    import ctypes
+    st = torch.cuda.current_stream().cuda_stream
+    steps = epochs * ((B + bs - 1) // bs)
+    ldb, in_dims = pad64(B), (2 * N, 3 * N, 2 * N)
+    geo = [(i, pad64(i * hid + hid + hid * hid + hid + hid + 1)) for i in in_dims]
+    # ---- the yardstick: one step = the eight launches of engine_adversaries._fit_critic_family on 32 rows
+    ldm = 64
+    z = lambda *s: torch.zeros(*s, device="cuda")
+    a1, a2, dz1, dz3, grads, lp = z(hid, ldm), z(hid, ldm), z(hid, ldm), z(ldm), z(L.rcmarl_wide_grad_size(hid)), z(4)
+    one = torch.ones(1, dtype=torch.int32, device="cuda")
+    per_step = []
+    for in_dim, ldp in geo:
+        th = torch.empty(ldp, device="cuda").uniform_(-0.1, 0.1)
+        xb, yb = torch.randn(bs, in_dim, device="cuda"), torch.randn(bs, device="cuda")
+        o_b1 = in_dim * hid
+        o_W2 = o_b1 + hid
+        o_b2 = o_W2 + hid * hid
+        p = lambda t: t.data_ptr()
+
+        def step():
+            L.rcmarl_dense_forward(p(xb), 0, 0, 1, in_dim, p(th), 0, o_b1, p(a1), 1, 1, bs, in_dim, hid, ldp, ldm, st)
+            L.rcmarl_dense_forward(p(a1), hid * ldm, hid * ldm, 0, ldm, p(th), o_W2, o_b2, p(a2), 1, 1, bs, hid, hid, ldp, ldm, st)
+            L.rcmarl_wide_head_fit(p(a2), p(th), p(yb), p(dz3), p(grads), p(lp), 1, 1, bs, in_dim, hid, ldp, ldm, st)
+            L.rcmarl_dense_backward_data(p(a2), p(th), o_W2, p(a1), p(dz1), 1, 1, bs, hid, hid, ldp, ldm, st)
+            L.rcmarl_wide_bias_grad(p(dz1), p(grads), 1, 1, bs, hid, ldm, st)
+            L.rcmarl_dense_backward_sgd(p(a1), hid * ldm, hid * ldm, 0, ldm, p(a2), p(th), o_W2, p(one), 1, 1, bs, hid, hid, ldp, ldm, 1e-4, st)
+            L.rcmarl_dense_backward_sgd(p(xb), 0, 0, 1, in_dim, p(dz1), p(th), 0, p(one), 1, 1, bs, in_dim, hid, ldp, ldm, 1e-4, st)
+            L.rcmarl_wide_small_sgd(p(grads), p(lp), p(th), p(one), None, 1, 1, bs, in_dim, hid, ldp, 1e-4, st)
+        t = timeit(step, iters=200, warm=20)
+        per_step.append(t)
+        print("launch-per-step loop, in=%2d hid=%d: %7.1f us per mini-batch step (eight launches)" % (in_dim, hid, t))
+    for S in (16, 512):
+        loop = sum(per_step) * steps * S
+        print("S=%3d: the loop's %d chains x %d steps, one after the other: %.0f ms (from the step times above)" % (S, 3 * S, steps, loop / 1e3))
+        if not hasattr(L, "rcmarl_minibatch_fit_wide"):
+            continue
+        jobs, keep = [], []
+        for in_dim, ldp in geo:
+            x, theta, y = torch.randn(S, B, in_dim, device="cuda"), torch.empty(S, N, ldp, device="cuda").uniform_(-0.1, 0.1), torch.randn(S, N, ldb, device="cuda")
+            agents = torch.tensor([N - 1], dtype=torch.int32, device="cuda")
+            perm = torch.stack([torch.stack([torch.randperm(B, device="cuda") for _ in range(epochs)]) for _ in range(S)]).to(torch.int32).reshape(S, 1, epochs, B).contiguous()
+            keep.append((x, theta, y, agents, perm))
+            jobs.append(capi.MbJob(x.data_ptr(), B * in_dim, theta.data_ptr(), agents.data_ptr(), 1, in_dim, ldp, 0, y.data_ptr(), perm.data_ptr(), None, None))
+        arr, hids = (capi.MbJob * 3)(*jobs), (ctypes.c_int * 3)(hid, hid, hid)
+        t = timeit(lambda: L.rcmarl_minibatch_fit_wide(arr, hids, 3, S, N, B, ldb, bs, epochs, 1e-4, st), iters=3, warm=1)
+        print("S=%3d: ONE rcmarl_minibatch_fit_wide launch (%d chains): %9.1f us = %.2f us per step of a chain in flight, %.3f us per step "
+              "and chain; %.0f x the loop" % (S, 3 * S, t, t / steps, t / steps / (3 * S), loop / t))
+
+
 if __name__ == "__main__":
     L = capi.CLib(os.environ["RCMARL_KBENCH_LIB"]) if os.environ.get("RCMARL_KBENCH_LIB") else capi.load()     # (variant builds)
     what = sys.argv[1] if len(sys.argv) > 1 else "gemm"
     print("== %s  RCMARL_GEMM=%s RCMARL_K1=%s" % (what, os.environ.get("RCMARL_GEMM"), os.environ.get("RCMARL_K1")))
-    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk, "rollout_wide": rollout_wide}[what](L)
+    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk, "rollout_wide": rollout_wide, "mb_wide": mb_wide}[what](L)
