@@ -262,6 +262,19 @@ int rcmarl_minibatch_fit_wide_supported(int in_dim, int hid, int batch_size);
 int rcmarl_minibatch_fit_wide(const rcmarl_mb_job* jobs, const int* hid, int njobs, int S, int N, int B, int ldb,
                               int batch_size, int epochs, float lr, void* stream);
 
+/* The same fits (agents/adversarial_CAC_agents.py:131-135,146-152,237-241) for the widths beyond rcmarl_minibatch_fit_wide's LDS
+ * layout (csrc/minibatch_wide2.hip): two activation images of a mini-batch instead of three (dz1 over a1), the layer-1 input chunks
+ * staged once per step.  Arguments, job structure, semantics and return codes are those of rcmarl_minibatch_fit_wide.
+ * rcmarl_minibatch_fit_wide2_supported: 1 exactly when in_dim > 0, 1 <= batch_size <= 32, rcmarl_minibatch_fit_wide_supported
+ *   answers 0 and the two-image layout fits the LDS: 384 < hid <= 576 (BASELINE configs[4]: 512).  The two queries never both answer
+ *   1; a width neither serves takes one launch per mini-batch step through the dense entry points.  Host-only.
+ * rcmarl_minibatch_fit_wide2 (agents/adversarial_CAC_agents.py:131-135,146-152,237-241): njobs (1..4) fits in ONE launch, one
+ *   workgroup per (job, seed, adversary); RCMARL_ERR_UNSUPPORTED for a job its query refuses, RCMARL_ERR_ARG as its sibling, both
+ *   before the HIP runtime is touched. */
+int rcmarl_minibatch_fit_wide2_supported(int in_dim, int hid, int batch_size);
+int rcmarl_minibatch_fit_wide2(const rcmarl_mb_job* jobs, const int* hid, int njobs, int S, int N, int B, int ldb,
+                               int batch_size, int epochs, float lr, void* stream);
+
 /* X1: one whole Keras fit() of the adversaries' networks per launch (one workgroup per (seed, adversary)).
  * agents: int[n_adv] agent indices; the rows theta[s][agents[k]] are trained IN PLACE.
  * perm: int[S][n_adv][epochs][B] row permutation per epoch (Keras shuffle; NULL = natural order).

@@ -42,6 +42,9 @@ SIGNATURES = {
     "rcmarl_minibatch_fit_wide_supported": [c_int, c_int, c_int],
     # jobs (host array of MbJob), hid (host int[njobs]), njobs, S, N, B, ldb, batch_size, epochs, lr, stream
     "rcmarl_minibatch_fit_wide": [C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_stream],
+    # the same two for the widths beyond that layout (csrc/minibatch_wide2.hip: 385 .. 576 units)
+    "rcmarl_minibatch_fit_wide2_supported": [c_int, c_int, c_int],
+    "rcmarl_minibatch_fit_wide2": [C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_stream],
     "rcmarl_lattice_forget": [c_u8p],
     "rcmarl_fit_partial_size": [c_int],
     "rcmarl_actor_partial_size": [c_int, c_int],
@@ -250,7 +253,8 @@ SIGNATURES = {
 UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_layout", "rcmarl_lattice_forget", "rcmarl_fit_partial_size", "rcmarl_lattice_set_f16_mode",  "rcmarl_actor_partial_size", "rcmarl_rows_per_chunk", "rcmarl_lattice_f16_mode",
              "rcmarl_wide_grad_size", "rcmarl_wide_rows_per_chunk", "rcmarl_wide_f16_mode", "rcmarl_wide_set_f16_mode",
              "rcmarl_consensus_params_circulant_supported", "rcmarl_pk_supported", "rcmarl_pk_parts",
-             "rcmarl_rollout_wide_supported", "rcmarl_minibatch_fit_wide_supported"}
+             "rcmarl_rollout_wide_supported", "rcmarl_minibatch_fit_wide_supported",
+             "rcmarl_minibatch_fit_wide2_supported"}
 
 ERRORS = {1: "RCMARL_ERR_ARG (bad argument)", 2: "RCMARL_ERR_LAUNCH (HIP launch failed)",
           3: "RCMARL_ERR_UNSUPPORTED (shape outside the compiled kernels)"}

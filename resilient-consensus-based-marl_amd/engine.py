@@ -65,7 +65,7 @@ class EngineConfig:
     def __init__(self, n_agents, agent_label, in_nodes, H=0, gamma=0.9, slow_lr=0.002, fast_lr=0.01, n_actions=5,
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
-                 local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID):
+                 local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID, adv_wide2="auto"):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -85,6 +85,11 @@ class EngineConfig:
         # hidden width of the team-reward nets: like the critic's, any other width than 20 runs the dense-GEMM path; the two widths
         # are independent of each other
         self.tr_hid = int(tr_hid)
+        # the adversaries' mini-batch fits of a 385 .. 576-unit net: "auto" (one rcmarl_minibatch_fit_wide2 launch per epoch from
+        # engine_adversaries.WIDE2_MIN_CHAINS chains on, the launch-per-step loop below) | True (the launch) | False (the loop)
+        if not any(adv_wide2 is v for v in (True, False)) and adv_wide2 != "auto":
+            raise ValueError("adv_wide2 must be 'auto', True or False")
+        self.adv_wide2 = adv_wide2
         assert len(self.agent_label) == self.n_agents and len(self.in_nodes) == self.n_agents
         if np.ndim(H) == 0:
             self.H_per_agent = [int(H)] * self.n_agents

@@ -21,10 +21,12 @@ keeps that shape: ALL such fits of a consensus epoch -- the Malicious agents' pr
 the transmitted team-reward net, the transmitted critic, for all seeds and adversaries -- are
 ONE rcmarl_minibatch_fit_wide launch (csrc/minibatch_wide.hip, one workgroup per chain, fp32 on
 the exact-f32 matrix instruction), beside rcmarl_minibatch_fit for a 20-unit net of the same
-engine.  Only a width the query does not serve (BASELINE configs[4]: 512 units) still takes
-the same mini-batch steps through the dense per-agent GEMM entry points (rcmarl_dense_*, one
-step = the eight launches of a wide local-fit step on 32 rows, chains one after the other in a
-Python loop): correct and slow.  Keras shuffles with TensorFlow's RNG; here the permutations come from
+engine.  The widths beyond that layout whose TWO activation images fit
+(rcmarl_minibatch_fit_wide2_supported: 385 .. 576 units, BASELINE configs[4]'s 512 among them) go
+the same way into ONE rcmarl_minibatch_fit_wide2 launch per epoch (csrc/minibatch_wide2.hip).  Only
+a width neither query serves (beyond 576 units) still takes the same mini-batch steps through the
+dense per-agent GEMM entry points (rcmarl_dense_*, one step = the eight launches of a wide
+local-fit step on 32 rows, chains one after the other in a Python loop): correct and slow.  Keras shuffles with TensorFlow's RNG; here the permutations come from
 a counter-based stream (csrc/shuffle.hip, generated on the device for all seeds at once; the oracle
 states the same definition), consumed in the reference's call order so that oracle and engine stay in
 lock step.
@@ -37,6 +39,13 @@ import torch
 HID = 20
 COOP, FAULTY, GREEDY, MALICIOUS = "Cooperative", "Faulty", "Greedy", "Malicious"
 FIT_BATCH, FIT_EPOCHS, ACTOR_BATCH = 32, 10, 200
+# Fewest chains (seeds x adversaries, summed over the epoch's fits of 385 .. 576 units) for which the one rcmarl_minibatch_fit_wide2
+# launch replaces the launch-per-step loop under EngineConfig(adv_wide2="auto").  A chain in the launch is bound by ONE compute unit,
+# the loop's steps use the whole chip but run one chain after the other.  Measured on an MI355X at 512 units, B = 2000, 10 epochs
+# (tools/kbench.py mb_wide --hid 512, docs/history/r11.md): the launch takes 308 ms for 2 and for 8 chains of 10 inputs against the
+# loop's 117 ms per chain (they cross at 3 chains), 1410 / 1430 ms for 2 / 8 chains of 2048 inputs against 222 ms per chain (they
+# cross at 7): from 7 chains on the launch is the faster one at both ends.
+WIDE2_MIN_CHAINS = 7
 
 
 class AdversaryPath:
@@ -283,10 +292,20 @@ class AdversaryPath:
         e = self.e
         return e.hid[net] != HID and e.lib.rcmarl_minibatch_fit_wide_supported(e.in_dim[net], e.hid[net], FIT_BATCH) == 1
 
+    def _wide2_served(self, net):
+        """this family's fits can go into the epoch's rcmarl_minibatch_fit_wide2 launch: a width beyond rcmarl_minibatch_fit_wide's
+        layout that the two-image layout holds (the library's own query; a library without the entry point serves none)"""
+        e = self.e
+        return (e.hid[net] != HID and hasattr(e.lib, "rcmarl_minibatch_fit_wide2_supported")
+                and e.lib.rcmarl_minibatch_fit_wide2_supported(e.in_dim[net], e.hid[net], FIT_BATCH) == 1)
+
     def _phase1_wide(self, B, perms):
         """phase I beside a wide net: every fit of the epoch whose net is wide and served -- the Malicious agents' private critic,
-        the transmitted team-reward net, the transmitted critic -- in ONE launch for all seeds and adversaries; a 20-unit net
-        beside them keeps rcmarl_minibatch_fit and an unserved width the launch-per-step loop (_fit_critic_family)."""
+        the transmitted team-reward net, the transmitted critic -- in ONE launch per entry point for all seeds and adversaries
+        (rcmarl_minibatch_fit_wide up to 384 units, rcmarl_minibatch_fit_wide2 from 385 to 576); a 20-unit net beside them keeps
+        rcmarl_minibatch_fit and an unserved width the launch-per-step loop (_fit_critic_family).  EngineConfig.adv_wide2: "auto"
+        sends the 385 .. 576-unit fits to their launch when the epoch has at least WIDE2_MIN_CHAINS such chains, True always, False
+        never (the loop)."""
         from . import capi
         e, L = self.e, self.e.lib
         fits = []                                      # the arguments of _fit_critic_family, in the reference's order
@@ -295,19 +314,26 @@ class AdversaryPath:
             fits.append((e.theta["critic_local"], self.mal_t, self.mal, e.ybuf["y_l"], perms["local"], B, None, "critic", "s", None))
         fits.append((e.theta["tr"], self.fit_t, self.fit, e.ybuf["r_fit"], perms["tr"], B, e.loss["tr"], "tr", "sa", "tr"))
         fits.append((e.theta["critic"], self.fit_t, self.fit, e.ybuf["y_c"], perms["critic"], B, e.loss["critic"], "critic", "s", None))
-        jobs, hids = [], []
-        for f in fits:
+        served = [self._wide_served(f[7]) for f in fits]
+        want2 = e.cfg.adv_wide2
+        served2 = [want2 is not False and not w and self._wide2_served(f[7]) for f, w in zip(fits, served)]
+        if want2 == "auto" and e.S * sum(len(f[2]) for f, w in zip(fits, served2) if w) < WIDE2_MIN_CHAINS:
+            served2 = [False] * len(fits)
+        launches = {"rcmarl_minibatch_fit_wide": ([], []), "rcmarl_minibatch_fit_wide2": ([], [])}
+        for f, w, w2 in zip(fits, served, served2):
             theta, agents_t, agents, y, perm, _, loss, net, xkey, _ = f
-            if not self._wide_served(net):
+            if not (w or w2):
                 self._fit_critic_family(*f)
                 continue
+            jobs, hids = launches["rcmarl_minibatch_fit_wide" if w else "rcmarl_minibatch_fit_wide2"]
             xptr, xstride = e._x(xkey)
             jobs.append(capi.MbJob(xptr, xstride, theta.data_ptr(), agents_t.data_ptr(), len(agents), e.in_dim[net], e.ldp[net], 0,
                                    y.data_ptr(), perm.data_ptr(), None if loss is None else loss.data_ptr(), None))
             hids.append(e.hid[net])
-        if jobs:
-            L.rcmarl_minibatch_fit_wide((capi.MbJob * len(jobs))(*jobs), (capi.c_int * len(hids))(*hids), len(jobs), e.S, e.N, B,
-                                        e.ldb, FIT_BATCH, FIT_EPOCHS, e.cfg.fast_lr, e.stream)
+        for name, (jobs, hids) in launches.items():
+            if jobs:
+                getattr(L, name)((capi.MbJob * len(jobs))(*jobs), (capi.c_int * len(hids))(*hids), len(jobs), e.S, e.N, B,
+                                 e.ldb, FIT_BATCH, FIT_EPOCHS, e.cfg.fast_lr, e.stream)
         self._publish("tr")                            # the fitted nets ARE the messages
         self._publish("critic")
 

@@ -6,7 +6,8 @@
     python tools/kbench.py k1_ragged # consensus_params_ragged on a degree mix against one masked uniform launch per class
     python tools/kbench.py mid       # mid_fit / consensus_head / mid_value
     python tools/kbench.py rollout_wide  # wide actor: one step of 50 episodes, matrix-core kernel vs plain kernel vs the weight stream
-    python tools/kbench.py mb_wide   # adversaries beside 64-unit nets: one rcmarl_minibatch_fit_wide launch vs the eight launches per step
+    python tools/kbench.py mb_wide [--hid 64] [--in-dim I --chains 2,8,64,256]   # adversaries beside wide nets: one mini-batch-fit launch
+                                     # (the entry point the library's queries name for the width) vs the eight launches per step
 """
 import os
 import sys
@@ -582,46 +583,101 @@ def rollout_wide(L, S=1, N=int(os.environ.get("RCMARL_KBENCH_N", "1024")), hid=5
     print("plain, %d single-state launches      %9.1f us  = %5.2f x the bound  (%.1f us per launch)" % (E, t, t / bound, t / E))
 
 
-def mb_wide(L, N=5, B=2000, hid=64, epochs=10, bs=32):
-    """the three chains a Malicious agent needs per consensus epoch beside 64-unit nets (private critic, team-reward net, critic:
-    10, 15 and 10 inputs), one adversary, for S seeds: ONE rcmarl_minibatch_fit_wide launch against the launch-per-step loop's eight
-    launches of one mini-batch step on a (seed, agent) = (1, 1) view (the yardstick; a library without the new entry point times
-    only that)"""
-    import ctypes
-    st = torch.cuda.current_stream().cuda_stream
-    steps = epochs * ((B + bs - 1) // bs)
-    ldb, in_dims = pad64(B), (2 * N, 3 * N, 2 * N)
-    geo = [(i, pad64(i * hid + hid + hid * hid + hid + hid + 1)) for i in in_dims]
-    # ---- the yardstick: one step = the eight launches of engine_adversaries._fit_critic_family on 32 rows
+def _mb_wide_entry(L, in_dim, hid, bs):
+    """the one-launch entry point that serves this shape, by the library's own queries (None: only the loop runs it)"""
+    if hasattr(L, "rcmarl_minibatch_fit_wide") and L.rcmarl_minibatch_fit_wide_supported(in_dim, hid, bs) == 1:
+        return "rcmarl_minibatch_fit_wide"
+    if hasattr(L, "rcmarl_minibatch_fit_wide2") and L.rcmarl_minibatch_fit_wide2_supported(in_dim, hid, bs) == 1:
+        return "rcmarl_minibatch_fit_wide2"
+    return None
+
+
+def _mb_wide_step_time(L, in_dim, hid, ldp, bs, st):
+    """the yardstick: one mini-batch step = the eight launches of engine_adversaries._fit_critic_family on a (seed, agent) = (1, 1)
+    view of 32 rows; us per step"""
     ldm = 64
     z = lambda *s: torch.zeros(*s, device="cuda")
     a1, a2, dz1, dz3, grads, lp = z(hid, ldm), z(hid, ldm), z(hid, ldm), z(ldm), z(L.rcmarl_wide_grad_size(hid)), z(4)
     one = torch.ones(1, dtype=torch.int32, device="cuda")
+    th = torch.empty(ldp, device="cuda").uniform_(-0.1, 0.1)
+    xb, yb = torch.randn(bs, in_dim, device="cuda"), torch.randn(bs, device="cuda")
+    o_b1 = in_dim * hid
+    o_W2 = o_b1 + hid
+    o_b2 = o_W2 + hid * hid
+    p = lambda t: t.data_ptr()
+
+    def step():
+        L.rcmarl_dense_forward(p(xb), 0, 0, 1, in_dim, p(th), 0, o_b1, p(a1), 1, 1, bs, in_dim, hid, ldp, ldm, st)
+        L.rcmarl_dense_forward(p(a1), hid * ldm, hid * ldm, 0, ldm, p(th), o_W2, o_b2, p(a2), 1, 1, bs, hid, hid, ldp, ldm, st)
+        L.rcmarl_wide_head_fit(p(a2), p(th), p(yb), p(dz3), p(grads), p(lp), 1, 1, bs, in_dim, hid, ldp, ldm, st)
+        L.rcmarl_dense_backward_data(p(a2), p(th), o_W2, p(a1), p(dz1), 1, 1, bs, hid, hid, ldp, ldm, st)
+        L.rcmarl_wide_bias_grad(p(dz1), p(grads), 1, 1, bs, hid, ldm, st)
+        L.rcmarl_dense_backward_sgd(p(a1), hid * ldm, hid * ldm, 0, ldm, p(a2), p(th), o_W2, p(one), 1, 1, bs, hid, hid, ldp, ldm, 1e-4, st)
+        L.rcmarl_dense_backward_sgd(p(xb), 0, 0, 1, in_dim, p(dz1), p(th), 0, p(one), 1, 1, bs, in_dim, hid, ldp, ldm, 1e-4, st)
+        L.rcmarl_wide_small_sgd(p(grads), p(lp), p(th), p(one), None, 1, 1, bs, in_dim, hid, ldp, 1e-4, st)
+    return timeit(step, iters=200, warm=20)
+
+
+def mb_wide(L, N=5, B=2000, epochs=10, bs=32):
+    """Adversaries beside wide nets: ONE launch of the mini-batch-fit entry point the library's queries name for the shape
+    (rcmarl_minibatch_fit_wide, rcmarl_minibatch_fit_wide2) against the launch-per-step loop's eight launches of one mini-batch step
+    (the yardstick; a library that serves the shape by no entry point times only that).
+
+        python tools/kbench.py mb_wide [--hid 64]                       # the three chains of a Malicious agent (10, 15, 10 inputs), S = 16, 512
+        python tools/kbench.py mb_wide --hid 512 --in-dim 2048 [--chains 2,8,64,256]
+                                                                        # one net of that shape, `chains` adversaries of one seed
+    With --in-dim the chains are adversaries of ONE seed (they share the replay rows, as the agents of a seed do) and the chain count
+    at which launch and loop cross is printed."""
+    import argparse
+    import ctypes
+    ap = argparse.ArgumentParser(prog="kbench.py mb_wide")
+    ap.add_argument("--hid", type=int, default=64)
+    ap.add_argument("--in-dim", type=int, default=None)
+    ap.add_argument("--chains", default="2,8,64,256")
+    args = ap.parse_args(sys.argv[2:])
+    hid = args.hid
+    st = torch.cuda.current_stream().cuda_stream
+    steps = epochs * ((B + bs - 1) // bs)
+    ldb = pad64(B)
+    width = lambda i: pad64(i * hid + hid + hid * hid + hid + hid + 1)
+    if args.in_dim is not None:
+        in_dim, ldp = args.in_dim, width(args.in_dim)
+        entry = _mb_wide_entry(L, in_dim, hid, bs)
+        t_step = _mb_wide_step_time(L, in_dim, hid, ldp, bs, st)
+        print("launch-per-step loop, in=%d hid=%d: %7.1f us per mini-batch step (eight launches); one-launch entry point: %s"
+              % (in_dim, hid, t_step, entry), flush=True)
+        x, cross = torch.randn(1, B, in_dim, device="cuda"), None
+        for chains in [int(c) for c in args.chains.split(",")]:
+            loop = t_step * steps * chains
+            if entry is None:
+                print("%3d chains x %d steps, one after the other: %.0f ms (from the step time above)" % (chains, steps, loop / 1e3))
+                continue
+            theta, y = torch.empty(1, chains, ldp, device="cuda").uniform_(-0.1, 0.1), torch.randn(1, chains, ldb, device="cuda")
+            agents = torch.arange(chains, dtype=torch.int32, device="cuda")
+            perm = torch.stack([torch.stack([torch.randperm(B, device="cuda") for _ in range(epochs)]) for _ in range(chains)]).to(torch.int32).reshape(1, chains, epochs, B).contiguous()
+            arr = (capi.MbJob * 1)(capi.MbJob(x.data_ptr(), 0, theta.data_ptr(), agents.data_ptr(), chains, in_dim, ldp, 0, y.data_ptr(), perm.data_ptr(), None, None))
+            hids = (ctypes.c_int * 1)(hid)
+            t = timeit(lambda: getattr(L, entry)(arr, hids, 1, 1, chains, B, ldb, bs, epochs, 1e-4, st), iters=3, warm=1)
+            if cross is None and t <= loop:
+                cross = chains
+            print("%3d chains: ONE %s launch %10.1f us = %7.2f us per step of a chain in flight; the loop's %d x %d steps %10.1f us "
+                  "(%7.2f us per step); loop / launch = %.2f" % (chains, entry, t, t / steps, chains, steps, loop, t_step, loop / t), flush=True)
+            del theta, y, perm
+        if entry is not None:
+            print("the launch is at least as fast as the loop from %s chains on (of those tried)" % (cross if cross is not None else "no count of"))
+        return
+    in_dims = (2 * N, 3 * N, 2 * N)
+    geo = [(i, width(i)) for i in in_dims]
     per_step = []
     for in_dim, ldp in geo:
-        th = torch.empty(ldp, device="cuda").uniform_(-0.1, 0.1)
-        xb, yb = torch.randn(bs, in_dim, device="cuda"), torch.randn(bs, device="cuda")
-        o_b1 = in_dim * hid
-        o_W2 = o_b1 + hid
-        o_b2 = o_W2 + hid * hid
-        p = lambda t: t.data_ptr()
-
-        def step():
-            L.rcmarl_dense_forward(p(xb), 0, 0, 1, in_dim, p(th), 0, o_b1, p(a1), 1, 1, bs, in_dim, hid, ldp, ldm, st)
-            L.rcmarl_dense_forward(p(a1), hid * ldm, hid * ldm, 0, ldm, p(th), o_W2, o_b2, p(a2), 1, 1, bs, hid, hid, ldp, ldm, st)
-            L.rcmarl_wide_head_fit(p(a2), p(th), p(yb), p(dz3), p(grads), p(lp), 1, 1, bs, in_dim, hid, ldp, ldm, st)
-            L.rcmarl_dense_backward_data(p(a2), p(th), o_W2, p(a1), p(dz1), 1, 1, bs, hid, hid, ldp, ldm, st)
-            L.rcmarl_wide_bias_grad(p(dz1), p(grads), 1, 1, bs, hid, ldm, st)
-            L.rcmarl_dense_backward_sgd(p(a1), hid * ldm, hid * ldm, 0, ldm, p(a2), p(th), o_W2, p(one), 1, 1, bs, hid, hid, ldp, ldm, 1e-4, st)
-            L.rcmarl_dense_backward_sgd(p(xb), 0, 0, 1, in_dim, p(dz1), p(th), 0, p(one), 1, 1, bs, in_dim, hid, ldp, ldm, 1e-4, st)
-            L.rcmarl_wide_small_sgd(p(grads), p(lp), p(th), p(one), None, 1, 1, bs, in_dim, hid, ldp, 1e-4, st)
-        t = timeit(step, iters=200, warm=20)
+        t = _mb_wide_step_time(L, in_dim, hid, ldp, bs, st)
         per_step.append(t)
         print("launch-per-step loop, in=%2d hid=%d: %7.1f us per mini-batch step (eight launches)" % (in_dim, hid, t))
+    entry = _mb_wide_entry(L, max(in_dims), hid, bs)
     for S in (16, 512):
         loop = sum(per_step) * steps * S
         print("S=%3d: the loop's %d chains x %d steps, one after the other: %.0f ms (from the step times above)" % (S, 3 * S, steps, loop / 1e3))
-        if not hasattr(L, "rcmarl_minibatch_fit_wide"):
+        if entry is None:
             continue
         jobs, keep = [], []
         for in_dim, ldp in geo:
@@ -631,9 +687,9 @@ def mb_wide(L, N=5, B=2000, hid=64, epochs=10, bs=32):
             keep.append((x, theta, y, agents, perm))
             jobs.append(capi.MbJob(x.data_ptr(), B * in_dim, theta.data_ptr(), agents.data_ptr(), 1, in_dim, ldp, 0, y.data_ptr(), perm.data_ptr(), None, None))
         arr, hids = (capi.MbJob * 3)(*jobs), (ctypes.c_int * 3)(hid, hid, hid)
-        t = timeit(lambda: L.rcmarl_minibatch_fit_wide(arr, hids, 3, S, N, B, ldb, bs, epochs, 1e-4, st), iters=3, warm=1)
-        print("S=%3d: ONE rcmarl_minibatch_fit_wide launch (%d chains): %9.1f us = %.2f us per step of a chain in flight, %.3f us per step "
-              "and chain; %.0f x the loop" % (S, 3 * S, t, t / steps, t / steps / (3 * S), loop / t))
+        t = timeit(lambda: getattr(L, entry)(arr, hids, 3, S, N, B, ldb, bs, epochs, 1e-4, st), iters=3, warm=1)
+        print("S=%3d: ONE %s launch (%d chains): %9.1f us = %.2f us per step of a chain in flight, %.3f us per step "
+              "and chain; %.0f x the loop" % (S, entry, 3 * S, t, t / steps, t / steps / (3 * S), loop / t))
 
 
 if __name__ == "__main__":
