@@ -162,6 +162,25 @@ int rcmarl_layer1_backward_sgd_lattice(const void* ktp, int ktp_rt, int ktp_kt, 
                                        const float* alpha, float* theta, const int* mask, int S, int N, int B,
                                        int in_dim, int hid, int ldp, float lr, void* wp_out, int wp_rt, int wp_kt,
                                        void* stream);
+/* The same step with the fp32 master copy of W1 kept, for the duration of one local fit, in a caller-owned scratch laid out in the
+ * order of the GEMM's accumulator tiles (whole 128-byte lines per wavefront access instead of four to six partial ones).  Between
+ * the steps of a fit nothing but this call reads the fp32 W1: the forward reads wp_out, the mid and small steps the small arrays.
+ *   src_tiled: W1 is read from w_tiled (else from theta);  dst_tiled: the updated W1 is written to w_tiled (else to theta).
+ *   One fit of n steps: step 0 (0, 1); steps 1 .. n-2 (1, 1); step n-1 (1, 0) with wp_out = NULL as usual; (0, 0) is
+ *   rcmarl_layer1_backward_sgd_lattice itself.  While W1 lives in the scratch, theta's W1 block is stale (the small arrays in theta
+ *   are not touched here and stay current); the (1, 0) step brings the rows of the unmasked agents up to date, a masked agent's row
+ *   is never written and its weights travel through the scratch unchanged.  Results are bit-identical to the strided sequence.
+ *   Layout: element (k, col = agent * hid + unit) of seed s at float index ((s KT + k/32) CT + col/32) 1024 + q 64 + lane with
+ *   lane = col%32 + 32 ((k%8)/4), q = 4 ((k%32)/8) + k%4, KT = 8 ceil(in_dim / 256), CT = 4 ceil(N hid / 128); the (0, 1) step
+ *   writes every position (zeros beyond in_dim / N hid).  w_tiled_bytes >= rcmarl_lattice_w1_tiled_bytes(S, N, in_dim, hid).
+ *   RCMARL_ERR_ARG (before any HIP call): a tiled role with w_tiled NULL or too small, dst_tiled without wp_out (W1 stays in the
+ *   scratch only when a forward follows, and that forward needs its operand). */
+int rcmarl_layer1_backward_sgd_lattice_tiled(const void* ktp, int ktp_rt, int ktp_kt, const void* dzp, int dzp_rt, int dzp_kt,
+                                             const float* alpha, float* theta, const int* mask, int S, int N, int B,
+                                             int in_dim, int hid, int ldp, float lr, void* wp_out, int wp_rt, int wp_kt,
+                                             float* w_tiled, long w_tiled_bytes, int src_tiled, int dst_tiled, void* stream);
+/* bytes of that scratch (host-only; -1 for a non-positive argument) */
+long rcmarl_lattice_w1_tiled_bytes(int S, int N, int in_dim, int hid);
 /* = rcmarl_mid_fit, but a1t is left intact and dz1 is written as dzp (its 16-bit pieces in the current operand form --
  * two f16 pieces of 2^8 dz1, or three exact bf16 pieces --, rows = (agent,unit) column, reduction = replay row, zero
  * beyond B) for rcmarl_layer1_backward_sgd_lattice.  With f16 backward operands the step itself runs on the f16 matrix

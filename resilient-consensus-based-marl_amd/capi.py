@@ -93,6 +93,10 @@ SIGNATURES = {
     # stream
     "rcmarl_layer1_backward_sgd_lattice": [c_u8p, c_int, c_int, c_u8p, c_int, c_int, c_f32p, c_f32p, c_u8p, c_int,
                                            c_int, c_int, c_int, c_int, c_int, c_float, c_u8p, c_int, c_int, c_stream],
+    # the same arguments up to wp_kt, then w_tiled, w_tiled_bytes, src_tiled, dst_tiled, stream
+    "rcmarl_layer1_backward_sgd_lattice_tiled": [c_u8p, c_int, c_int, c_u8p, c_int, c_int, c_f32p, c_f32p, c_u8p, c_int,
+                                                 c_int, c_int, c_int, c_int, c_int, c_float, c_u8p, c_int, c_int, c_f32p, c_long,
+                                                 c_int, c_int, c_stream],
     # a1t, theta, y, partials, dzp, dzp_rt, dzp_kt, S, N, B, in_dim, hid, ldp, ldb, ovf_flags, stream
     "rcmarl_mid_fit_lattice": [c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                c_int, c_int, c_i32p, c_stream],
@@ -256,6 +260,12 @@ UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_
              "rcmarl_rollout_wide_supported", "rcmarl_minibatch_fit_wide_supported",
              "rcmarl_minibatch_fit_wide2_supported"}
 
+# host-only size queries that return long (bytes), not a status: name -> argtypes
+LONG_QUERIES = {
+    # S, N, in_dim, hid
+    "rcmarl_lattice_w1_tiled_bytes": [c_int, c_int, c_int, c_int],
+}
+
 ERRORS = {1: "RCMARL_ERR_ARG (bad argument)", 2: "RCMARL_ERR_LAUNCH (HIP launch failed)",
           3: "RCMARL_ERR_UNSUPPORTED (shape outside the compiled kernels)"}
 
@@ -294,6 +304,11 @@ class CLib:
             fn.argtypes = argtypes
             fn.restype = C.c_int
             setattr(self, name, fn if name in UNCHECKED else self._checked(name, fn))
+        for name, argtypes in LONG_QUERIES.items():
+            fn = getattr(self._dll, name)
+            fn.argtypes = argtypes
+            fn.restype = C.c_long
+            setattr(self, name, fn)
 
     @staticmethod
     def _checked(name, fn):

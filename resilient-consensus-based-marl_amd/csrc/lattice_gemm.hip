@@ -381,13 +381,27 @@ void k_lat_forward(const unsigned char* __restrict__ wp, int wp_rt, int wp_kt, c
 // W8 (eight wavefronts of 64 x 64): 780 / 1103 against 756 / 1103 us -- the alternative.
 // M128 (four-wavefront form only): 128 x 128 block tiles for networks of at most 128 inputs (BASELINE configs[2]'s critic: 64 agents,
 // 128 inputs) -- the 256-row tile would spend half its matrix work on rows beyond the input width.
-template <bool W8, bool DZ16, bool WP16, bool M128 = false>
+//
+// ROLE: where the fp32 master copy of W1 is read (bit 0) and written (bit 1): 0 = the strided parameter rows (theta), 1 = the TILED
+// scratch w_tiled.  Between the SGD steps of one local fit nothing but this kernel reads the fp32 W1 (the forward reads wp_out, the mid
+// step and the small step the small arrays), so for the duration of a fit it may live in the order the accumulators already have:
+// element (k, col) of seed s at float index ((s KT + k/32) CT + col/32) 1024 + q 64 + lane, lane = col%32 + 32 ((k%8)/4),
+// q = 4 ((k%32)/8) + k%4 -- one (m-tile, n-tile, register) access of a wavefront is 256 contiguous bytes = two whole 128-B lines,
+// where a strided access touches four to six partial lines (a lane's column is one (agent, unit); rows are 80 B apart).  KT / CT: the
+// extents in 32-row / 32-column units, padded to 256 rows / 128 columns, so every tile of every form (W8, four waves, M128) lies inside.
+//   ROLE 2 (strided -> tiled, first step): writes EVERY position of its tiles -- zeros beyond in_dim / N hid, a masked agent's unchanged
+//           weights -- so the tiled reads of the later steps need no predicates (alpha is 0 out there: 0 x garbage would put NaN into
+//           wp_out's padding rows);  ROLE 3 (tiled -> tiled);  ROLE 1 (tiled -> strided, last step: a masked agent's row is not written).
+// The arithmetic of every element is that of ROLE 0: bit-identical results.  Measured at the cfg-4 shapes (docs/history/r12.md): a
+// tiled -> tiled launch 466-473 / 684-689 us against 497-512 / 732-745 for ROLE 0; all roles in registers, no scratch, same occupancy.
+template <bool W8, bool DZ16, bool WP16, bool M128 = false, int ROLE = 0>
 __global__ RC_LAT_OCC(W8 ? 512 : 256, W8 ? 4 : 2)
 void k_lat_backward_sgd(const unsigned char* __restrict__ ktp, int ktp_rt, int ktp_kt, const unsigned char* __restrict__ dzp,
                         int dzp_rt, int dzp_kt, const float* __restrict__ alpha, float* __restrict__ theta,
                         const int* __restrict__ mask, int S, int N, int B, int in_dim, int ldp, float lr, int mtiles, int ntiles,
-                        unsigned char* __restrict__ wp_out, int wp_rt, int wp_kt, int hid) {
+                        unsigned char* __restrict__ wp_out, int wp_rt, int wp_kt, int hid, float* __restrict__ w_tiled) {
   static_assert(!(W8 && M128), "the 128-row tile exists in the four-wavefront form");
+  constexpr bool SRC_T = (ROLE & 1) != 0, DST_T = (ROLE & 2) != 0;
   constexpr int PA = 1, PB = DZ16 ? 2 : 3, MT = W8 ? 2 : (M128 ? 2 : 4), NT = 2, WM = W8 ? 4 : 2, WN = 2;
   constexpr int WNP = WP16 ? 2 : 3;                                 // pieces of the forward operand written by the epilogue
   typedef LatCfg<PA, PB, MT, NT, WM, WN> C;
@@ -430,6 +444,12 @@ void k_lat_backward_sgd(const unsigned char* __restrict__ ktp, int ktp_rt, int k
     // the lane's first row: k = bm*BM + wm*32*MT + 4*half; rows of (mt, gq, e) follow at uniform distances
     const int k0 = bm * C::BM + wm * 32 * MT + 4 * half;
     float* th = theta + ((long)s * N + ag) * ldp + j + (long)k0 * hid;
+    // the tiled home of the lane's (mt, q = 0) element: registers q follow 64 floats apart, m-tiles CT * 1024
+    const long tl_mt = (long)(ntiles * 4) * 1024;
+    float* tl = nullptr;
+    (void)tl_mt; (void)tl; (void)th;
+    if constexpr (SRC_T || DST_T)
+      tl = w_tiled + (((long)s * (((in_dim + 255) >> 8) * 8) + (bm * (C::BM / 32) + wm * MT)) * (ntiles * 4) + (bn * (C::BN / 32) + wn * NT + nt)) * 1024 + lane;
     // The forward operand of the next step: a lane's four consecutive k of one (mt, gq) are HALF a 16-byte chunk of the packed row
     // (the other half sits in lane ^ 32).  Round 5: the two lanes exchange halves (one v_permlane32_swap per dword) so that each
     // stores WHOLE chunks -- lane half 0 the even gq, half 1 the odd ones -- as 16-byte stores: half the store instructions and half
@@ -448,7 +468,8 @@ void k_lat_backward_sgd(const unsigned char* __restrict__ ktp, int ktp_rt, int k
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int dk = 32 * mt + 8 * (q >> 2) + (q & 3);               // uniform
-        wold[mt][q] = (act && (full_k || k0 + dk < in_dim)) ? th[(long)dk * hid] : 0.f;
+        if constexpr (SRC_T) wold[mt][q] = tl[mt * tl_mt + q * 64];
+        else wold[mt][q] = (act && (full_k || k0 + dk < in_dim)) ? th[(long)dk * hid] : 0.f;
       }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -468,8 +489,9 @@ void k_lat_backward_sgd(const unsigned char* __restrict__ ktp, int ktp_rt, int k
             float w = wold[mt][4 * gq + e];
             if (upd && (full_k || k0 + dk < in_dim)) {
               w = w - lr * (av[e] * acc[mt][nt][4 * gq + e]);
-              th[(long)dk * hid] = w;
+              if constexpr (!DST_T) th[(long)dk * hid] = w;
             }
+            if constexpr (DST_T) tl[mt * tl_mt + (4 * gq + e) * 64] = w;
             wn4[e] = w * av[e];
           }
           if constexpr (WP16) {
@@ -520,17 +542,29 @@ int launch_forward(unsigned nblocks, void* stream, const unsigned char* wp, int 
   return rcmarl_check_launch();
 }
 
-template <bool W8, bool DZ16, bool WP16, bool M128 = false>
-int launch_backward(unsigned nblocks, void* stream, const unsigned char* ktp, int ktp_rt, int ktp_kt, const unsigned char* dzp,
-                    int dzp_rt, int dzp_kt, const float* alpha, float* theta, const int* mask, int S, int N, int B, int in_dim,
-                    int ldp, float lr, int mtiles, int ntiles, unsigned char* wp_out, int wp_rt, int wp_kt, int hid) {
+template <bool W8, bool DZ16, bool WP16, bool M128, int ROLE>
+int launch_backward_role(unsigned nblocks, void* stream, const unsigned char* ktp, int ktp_rt, int ktp_kt, const unsigned char* dzp,
+                         int dzp_rt, int dzp_kt, const float* alpha, float* theta, const int* mask, int S, int N, int B, int in_dim,
+                         int ldp, float lr, int mtiles, int ntiles, unsigned char* wp_out, int wp_rt, int wp_kt, int hid,
+                         float* w_tiled) {
   const size_t smem = (size_t)2 * LatCfg<1, DZ16 ? 2 : 3, 4, 2>::STAGE_BYTES;
-  static const bool ok = rc_want_lds(k_lat_backward_sgd<W8, DZ16, WP16, M128>, smem);
+  static const bool ok = rc_want_lds(k_lat_backward_sgd<W8, DZ16, WP16, M128, ROLE>, smem);
   if (!ok) return RCMARL_ERR_LAUNCH;
-  RCMARL_LAUNCH((k_lat_backward_sgd<W8, DZ16, WP16, M128>), dim3(nblocks), dim3(W8 ? 512 : 256), smem, stream, ktp, ktp_rt, ktp_kt, dzp,
-                dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, ldp, DZ16 ? lr * RC_F16_DZ_UNSCALE : lr, mtiles, ntiles,
-                wp_out, wp_rt, wp_kt, hid);
+  RCMARL_LAUNCH((k_lat_backward_sgd<W8, DZ16, WP16, M128, ROLE>), dim3(nblocks), dim3(W8 ? 512 : 256), smem, stream, ktp, ktp_rt, ktp_kt,
+                dzp, dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, ldp, DZ16 ? lr * RC_F16_DZ_UNSCALE : lr, mtiles, ntiles,
+                wp_out, wp_rt, wp_kt, hid, w_tiled);
   return rcmarl_check_launch();
+}
+
+// role: bit 0 = W1 is read from w_tiled, bit 1 = W1 is written to w_tiled (k_lat_backward_sgd)
+template <bool W8, bool DZ16, bool WP16, bool M128 = false, typename... A>
+int launch_backward(int role, A... a) {
+  switch (role) {
+    case 0: return launch_backward_role<W8, DZ16, WP16, M128, 0>(a...);
+    case 1: return launch_backward_role<W8, DZ16, WP16, M128, 1>(a...);
+    case 2: return launch_backward_role<W8, DZ16, WP16, M128, 2>(a...);
+    default: return launch_backward_role<W8, DZ16, WP16, M128, 3>(a...);
+  }
 }
 
 }  // namespace
@@ -654,14 +688,25 @@ RCMARL_EXPORT int rcmarl_layer1_forward_lattice_pk(const void* kp, int kp_rt, in
                                           nullptr, S, N, B, in_dim, ldp, 64, mtiles, ntiles, hid, pk);
 }
 
+// bytes of the tiled fp32 W1 scratch of k_lat_backward_sgd's tiled roles: [S][KT][CT] blocks of 32 x 32 floats
+static long lat_w1_tiled_bytes(int S, int N, int in_dim, int hid) {
+  if (S <= 0 || N <= 0 || in_dim <= 0 || hid <= 0) return -1;
+  const long kt = (long)rc_ceil_div(in_dim, 256) * 8, ct = ((long)N * hid + 127) / 128 * 4;
+  return (long)S * kt * ct * 4096;
+}
+
 static int backward_sgd_lattice_impl(const void* ktp, int ktp_rt, int ktp_kt, const void* dzp, int dzp_rt,
                                                      int dzp_kt, const float* alpha, float* theta, const int* mask,
                                                      int S, int N, int B, int in_dim, int hid, int ldp, float lr,
-                                                     void* wp_out, int wp_rt, int wp_kt, void* stream) {
+                                                     void* wp_out, int wp_rt, int wp_kt, void* stream,
+                                                     float* w_tiled = nullptr, long w_tiled_bytes = 0, int role = 0) {
   if (!ktp || !dzp || !alpha || !theta || S <= 0 || N <= 0 || B <= 0 || in_dim <= 0 || (ldp & 63) ||
       ldp < in_dim * hid + hid)
     return RCMARL_ERR_ARG;
   if (hid <= 0) return RCMARL_ERR_ARG;
+  if (role != 0 && (!w_tiled || (reinterpret_cast<uintptr_t>(w_tiled) & 3) || w_tiled_bytes < lat_w1_tiled_bytes(S, N, in_dim, hid)))
+    return RCMARL_ERR_ARG;
+  if ((role & 2) && !wp_out) return RCMARL_ERR_ARG;                  // W1 stays in the scratch: a forward follows and needs its operand
   const bool w8 = lat_w8(false);
   const int m128_env = lat_env_int("RCMARL_LAT_M128", 1);           // 1: 128-row tiles up to 128 inputs; 0: never; 2: always (measurement)
   const bool m128 = !w8 && ((in_dim <= 128 && m128_env != 0) || m128_env == 2);
@@ -674,15 +719,15 @@ static int backward_sgd_lattice_impl(const void* ktp, int ktp_rt, int ktp_kt, co
   if (!rc_form_ok(ktp, (mode >> 1) & 1) || !rc_form_ok(dzp, (mode >> 1) & 1)) return RCMARL_ERR_ARG;   // written in the other operand form
   rc_form_set(wp_out, mode & 1);
 #define RC_BWD(W8, DZ16, WP16)                                                                                              \
-  launch_backward<W8, DZ16, WP16>(nb, stream, (const unsigned char*)ktp, ktp_rt, ktp_kt, (const unsigned char*)dzp, dzp_rt, \
-                                  dzp_kt, alpha, theta, mask, S, N, B, in_dim, ldp, lr, mtiles, ntiles,                     \
-                                  (unsigned char*)wp_out, wp_rt, wp_kt, hid)
+  launch_backward<W8, DZ16, WP16>(role, nb, stream, (const unsigned char*)ktp, ktp_rt, ktp_kt, (const unsigned char*)dzp, dzp_rt, \
+                                  dzp_kt, alpha, theta, mask, S, N, B, in_dim, ldp, lr, mtiles, ntiles,                           \
+                                  (unsigned char*)wp_out, wp_rt, wp_kt, hid, w_tiled)
   // at most 128 inputs: 128-row tiles (RCMARL_LAT_M128=0 keeps the 256-row tile)
   if (m128) {
 #define RC_BWD128(DZ16, WP16)                                                                                                  \
-  launch_backward<false, DZ16, WP16, true>(nb, stream, (const unsigned char*)ktp, ktp_rt, ktp_kt, (const unsigned char*)dzp,  \
-                                           dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, ldp, lr, mtiles, ntiles,       \
-                                           (unsigned char*)wp_out, wp_rt, wp_kt, hid)
+  launch_backward<false, DZ16, WP16, true>(role, nb, stream, (const unsigned char*)ktp, ktp_rt, ktp_kt, (const unsigned char*)dzp,  \
+                                           dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, ldp, lr, mtiles, ntiles,             \
+                                           (unsigned char*)wp_out, wp_rt, wp_kt, hid, w_tiled)
     switch (mode) {
       case 0: return RC_BWD128(false, false);
       case 1: return RC_BWD128(false, true);
@@ -710,4 +755,15 @@ RCMARL_EXPORT int rcmarl_layer1_backward_sgd_lattice(const void* ktp, int ktp_rt
                                                      void* wp_out, int wp_rt, int wp_kt, void* stream) {
   return backward_sgd_lattice_impl(ktp, ktp_rt, ktp_kt, dzp, dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, hid, ldp, lr, wp_out,
                                    wp_rt, wp_kt, stream);
+}
+
+RCMARL_EXPORT long rcmarl_lattice_w1_tiled_bytes(int S, int N, int in_dim, int hid) { return lat_w1_tiled_bytes(S, N, in_dim, hid); }
+
+RCMARL_EXPORT int rcmarl_layer1_backward_sgd_lattice_tiled(const void* ktp, int ktp_rt, int ktp_kt, const void* dzp, int dzp_rt,
+                                                           int dzp_kt, const float* alpha, float* theta, const int* mask,
+                                                           int S, int N, int B, int in_dim, int hid, int ldp, float lr,
+                                                           void* wp_out, int wp_rt, int wp_kt, float* w_tiled, long w_tiled_bytes,
+                                                           int src_tiled, int dst_tiled, void* stream) {
+  return backward_sgd_lattice_impl(ktp, ktp_rt, ktp_kt, dzp, dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, hid, ldp, lr, wp_out,
+                                   wp_rt, wp_kt, stream, w_tiled, w_tiled_bytes, (src_tiled ? 1 : 0) | (dst_tiled ? 2 : 0));
 }

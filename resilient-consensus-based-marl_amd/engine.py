@@ -26,6 +26,8 @@ from . import lattice as LT
 
 HID = 20
 COOP, FAULTY, GREEDY, MALICIOUS = "Cooperative", "Faulty", "Greedy", "Malicious"
+# EngineConfig(w1_tiled="auto"): what the measurement of docs/history/r12.md decided
+W1_TILED_AUTO = True
 
 
 def pad64(n):
@@ -65,7 +67,8 @@ class EngineConfig:
     def __init__(self, n_agents, agent_label, in_nodes, H=0, gamma=0.9, slow_lr=0.002, fast_lr=0.01, n_actions=5,
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
-                 local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID, adv_wide2="auto"):
+                 local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID, adv_wide2="auto",
+                 w1_tiled="auto"):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -90,6 +93,11 @@ class EngineConfig:
         if not any(adv_wide2 is v for v in (True, False)) and adv_wide2 != "auto":
             raise ValueError("adv_wide2 must be 'auto', True or False")
         self.adv_wide2 = adv_wide2
+        # local fits of the 20-unit nets on the lattice path: the fp32 W1 of the message lives in accumulator-tile order between the
+        # SGD steps of a fit (rcmarl_layer1_backward_sgd_lattice_tiled): "auto" (see W1_TILED_AUTO) | True | False
+        if not any(w1_tiled is v for v in (True, False)) and w1_tiled != "auto":
+            raise ValueError("w1_tiled must be 'auto', True or False")
+        self.w1_tiled = w1_tiled
         assert len(self.agent_label) == self.n_agents and len(self.in_nodes) == self.n_agents
         if np.ndim(H) == 0:
             self.H_per_agent = [int(H)] * self.n_agents
@@ -754,6 +762,15 @@ class RPBCACEngine:
                           "sa": torch.tensor(LT.column_alpha(self.N, 3, c.nrow, c.ncol, c.scaling), **f32)}
         self.lat_alpha["ns"] = self.lat_alpha["s"]
         self.lat_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        # fp32 W1 of a 20-unit message in accumulator-tile order between the SGD steps of its local fit: ONE scratch sized by the
+        # larger family (the two fits run one after the other on one stream; cfg 4: 16 x 768 x 5120 x 4 B = 252 MB).  Its address is
+        # fixed for the engine's life, so captured epochs replay unchanged; an agent window indexes it from its base with its own N.
+        want = W1_TILED_AUTO if c.w1_tiled == "auto" else c.w1_tiled
+        fams = [net for net in ("critic", "tr") if self.hid[net] == HID]
+        self.lat_w1_tiled = None
+        if want and c.local_fit_steps >= 2 and fams:
+            nbytes = max(int(self.lib.rcmarl_lattice_w1_tiled_bytes(self.S, self.N, self.in_dim[net], HID)) for net in fams)
+            self.lat_w1_tiled = torch.zeros(nbytes // 4, **f32)
         # the last next-state row of every episode (the TD target's own forward pass, _value_next_cached): a small image of its own
         self.lat_geom_term = LT.Geometry(self.N, self.in_c, max(1, -(-self.cap // max(c.max_ep_len, 1))), self.hid["critic"])
         self.lat_kp_term = u8(self.lat_geom_term.kp, 1)
@@ -1181,11 +1198,17 @@ class RPBCACEngine:
                 # the epilogue also leaves the bf16x3 split of the updated W1 for the NEXT step's forward -- except after
                 # the last step, whose weights only travel as a message (252 / 378 MB of writes per fit at cfg 4)
                 last = step == self.cfg.local_fit_steps - 1
-                L.rcmarl_layer1_backward_sgd_lattice(self.lat_ktp[xkey].data_ptr(), g.ktp[0], g.ktp[1],
-                                                     dzp.data_ptr(), g.dzp[0], g.dzp[1],
-                                                     self.lat_alpha[xkey].data_ptr(), msg.data_ptr(), mask.data_ptr(), S, N,
-                                                     B, self.in_dim[net], HID, self.ldp[net], self.cfg.fast_lr,
-                                                     None if last else wp.data_ptr(), g.wp[0], g.wp[1], self.stream)
+                args = (self.lat_ktp[xkey].data_ptr(), g.ktp[0], g.ktp[1], dzp.data_ptr(), g.dzp[0], g.dzp[1],
+                        self.lat_alpha[xkey].data_ptr(), msg.data_ptr(), mask.data_ptr(), S, N, B, self.in_dim[net], HID,
+                        self.ldp[net], self.cfg.fast_lr, None if last else wp.data_ptr(), g.wp[0], g.wp[1])
+                wt = self.lat_w1_tiled
+                if wt is not None and self.cfg.local_fit_steps >= 2:
+                    # between the steps the fp32 W1 lives in accumulator-tile order (nothing else reads it before the fit ends):
+                    # step 0 strided -> tiled, the middle steps tiled -> tiled, the last one tiled -> strided
+                    L.rcmarl_layer1_backward_sgd_lattice_tiled(*args, wt.data_ptr(), 4 * wt.numel(), int(step > 0), int(not last),
+                                                               self.stream)
+                else:
+                    L.rcmarl_layer1_backward_sgd_lattice(*args, self.stream)
                 wp_fresh = True           # the epilogue left the split of the updated W1 in lat_wp
             else:
                 L.rcmarl_layer1_backward_sgd(ptr, stride, a1.data_ptr(), msg.data_ptr(), mask.data_ptr(), S, N, B,

@@ -40,6 +40,7 @@ WORK = {
     # lattice path: fp32-EQUIVALENT flops 2*M*N*K (the kernel executes 2x that on the f16 matrix core, 3x in the bf16 form)
     "rcmarl_layer1_forward_lattice": lambda a: _gemm_flops(a, 8),
     "rcmarl_layer1_backward_sgd_lattice": lambda a: _gemm_flops(a, 9),
+    "rcmarl_layer1_backward_sgd_lattice_tiled": lambda a: _gemm_flops(a, 9),      # (the same step, W1 in the tiled scratch)
     # a1t, theta, y, partials, dzp, rt, kt, S, N, B, in_dim, hid: reads a1 (4 B), writes the 16-bit pieces of dz1 (2 x 2 B, or 3 x 2 B)
     "rcmarl_mid_fit_lattice": lambda a: (a[7] * a[8] * a[9] * (8.0 * a[11] ** 2 + 12.0 * a[11]),
                                          (4.0 + 2.0 * lattice_pieces(2)) * a[7] * a[8] * a[9] * a[11]),
@@ -80,6 +81,8 @@ class TimedLib:
         for name in capi.SIGNATURES:
             fn = getattr(lib, name)
             setattr(self, name, fn if name in capi.UNCHECKED else self._wrap(name, fn))
+        for name in capi.LONG_QUERIES:
+            setattr(self, name, getattr(lib, name))
 
     def _wrap(self, name, fn):
         def call(*args):

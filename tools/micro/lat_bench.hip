@@ -5,7 +5,10 @@
 //
 //   hipcc --offload-arch=gfx950 -O2 tools/micro/lat_bench.hip -o tools/micro/lat_bench -ldl
 //   tools/micro/lat_bench LIB.so fwd|bwd|both  "RCMARL_LAT_PERSIST=0" "RCMARL_LAT_PERSIST=1,RCMARL_LAT_STAGGER=4" ...
-// env: LB_S (16) LB_N (256) LB_B (3000) LB_ITERS (20) LB_WIDTHS ("2,3")
+//   LB_PARENT=PARENT.so tools/micro/lat_bench LIB.so seq "RCMARL_LAT_W8=0"     the five backward launches of one local fit: the strided
+//                                             entry point (of the parent build and of LIB) against LIB's tiled roles -- word compare of
+//                                             Wp after every step and of theta after the last, then us per launch by role
+// env: LB_S (16) LB_N (256) LB_B (3000) LB_ITERS (20) LB_WIDTHS ("2,3") LB_REPS (3, seq only)
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <stdio.h>
@@ -22,9 +25,9 @@ typedef int (*packdz_t)(const float*, void*, int, int, int, int, int, int, int, 
 typedef int (*fwd_t)(const void*, int, int, const void*, int, int, const float*, float*, int, int, int, int, int, int, int, void*);
 typedef int (*bwd_t)(const void*, int, int, const void*, int, int, const float*, float*, const int*, int, int, int, int, int, int, float,
                      void*, int, int, void*);
-typedef int (*bwdws_t)(const void*, int, int, const void*, int, int, const float*, float*, const int*, int, int, int, int, int, int, float,
-                       void*, int, int, void*, long, void*);
-typedef long (*wsbytes_t)(int, int, int, int, int);
+typedef int (*bwdt_t)(const void*, int, int, const void*, int, int, const float*, float*, const int*, int, int, int, int, int, int, float,
+                      void*, int, int, float*, long, int, int, void*);
+typedef long (*tbytes_t)(int, int, int, int);
 
 __device__ __forceinline__ unsigned hash32(unsigned x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
@@ -75,7 +78,7 @@ static int cdiv(int a, int b) { return (a + b - 1) / b; }
 static int pad64(int a) { return (a + 63) / 64 * 64; }
 
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: %s LIB.so fwd|bwd|both CONFIG...\n", argv[0]); return 1; }
+  if (argc < 4) { fprintf(stderr, "usage: %s LIB.so fwd|bwd|both|seq CONFIG...\n", argv[0]); return 1; }
   void* h = dlopen(argv[1], RTLD_NOW);
   if (!h) { fprintf(stderr, "dlopen: %s\n", dlerror()); return 1; }
   const std::string what = argv[2];
@@ -84,8 +87,8 @@ int main(int argc, char** argv) {
   packdz_t packdz = (packdz_t)dlsym(h, "rcmarl_lattice_pack_dz");
   fwd_t fwd0 = (fwd_t)dlsym(h, "rcmarl_layer1_forward_lattice");
   bwd_t bwd0 = (bwd_t)dlsym(h, "rcmarl_layer1_backward_sgd_lattice");
-  bwdws_t bwdws0 = (bwdws_t)dlsym(h, "rcmarl_layer1_backward_sgd_lattice_ws");
-  wsbytes_t wsbytes = (wsbytes_t)dlsym(h, "rcmarl_lattice_backward_workspace_bytes");
+  bwdt_t bwdt = (bwdt_t)dlsym(h, "rcmarl_layer1_backward_sgd_lattice_tiled");
+  tbytes_t tbytes = (tbytes_t)dlsym(h, "rcmarl_lattice_w1_tiled_bytes");
   if (!enc || !split || !packdz || !fwd0 || !bwd0) { fprintf(stderr, "missing symbols\n"); return 1; }
   const int S = envi("LB_S", 16), N = envi("LB_N", 256), B = envi("LB_B", 3000), HID = 20, iters = envi("LB_ITERS", 20);
   const char* widths = getenv("LB_WIDTHS") ? getenv("LB_WIDTHS") : "2,3";
@@ -137,26 +140,111 @@ int main(int argc, char** argv) {
     int hflag = 0;
     CK(hipMemcpy(&hflag, flag, 4, hipMemcpyDeviceToHost));
     printf("== in_dim %d: producers rc=%d lattice-flag=%d\n", in_dim, rc, hflag);
-    long ws_bytes = wsbytes ? wsbytes(S, N, B, in_dim, HID) : 0;
-    void* ws = nullptr;
-    if (ws_bytes > 0) { CK(hipMalloc(&ws, ws_bytes)); CK(hipMemset(ws, 0, ws_bytes)); }
     const double flops = 2.0 * S * N * HID * (double)B * in_dim;
 
-    for (int ci = 3; ci < argc; ++ci) {
+    if (what == "seq") {
+      // The five backward launches of ONE local fit (a distinct dz1 per step; wp_out on all but the last), three ways: the strided entry
+      // point of the PARENT build (LB_PARENT=its .so: the yardstick), the strided entry point of this build, and this build's tiled roles
+      // (strided -> tiled, 3 x tiled -> tiled, tiled -> strided).  First the word compare -- Wp after every step, theta after the last --
+      // then LB_REPS (3) repetitions alternating the three, LB_ITERS fits each, every launch between two events: us per launch by role.
+      const int STEPS = 5, reps = envi("LB_REPS", 3);
+      for (int ci = 3; ci < argc; ++ci) {
+        const auto kv = parse_cfg(argv[ci]);
+        for (auto& p : kv) setenv(p.first.c_str(), p.second.c_str(), 1);
+        if (!bwdt || !tbytes) { fprintf(stderr, "seq: the library has no tiled entry point\n"); return 1; }
+        bwd_t bwdp = nullptr;
+        void* hp = nullptr;
+        if (getenv("LB_PARENT")) {
+          hp = dlopen(getenv("LB_PARENT"), RTLD_NOW | RTLD_LOCAL);
+          if (!hp) { fprintf(stderr, "dlopen %s: %s\n", getenv("LB_PARENT"), dlerror()); return 1; }
+          bwdp = (bwd_t)dlsym(hp, "rcmarl_layer1_backward_sgd_lattice");
+          if (!bwdp) { fprintf(stderr, "LB_PARENT: missing symbols\n"); return 1; }
+        }
+        unsigned char* dzps[STEPS];
+        for (int st = 0; st < STEPS; ++st) {
+          CK(hipMalloc(&dzps[st], dzp_b));
+          CK(hipMemset(dzps[st], 0, dzp_b));
+          hipLaunchKernelGGL(k_init_uniform, dim3(4096), dim3(256), 0, 0, dz, n_a1, 2e-3f, 4242u + 17u * st + width);
+          rc |= packdz(dz, dzps[st], S, N, B, HID, ldb, dzp_rt, dzp_kt, nullptr);
+        }
+        CK(hipDeviceSynchronize());
+        const long wt_bytes = tbytes(S, N, in_dim, HID);
+        float* wt;
+        CK(hipMalloc(&wt, wt_bytes));
+        CK(hipMemset(wt, 0xff, wt_bytes));                     // NaN: the first step must write what the later ones read
+        enum { PARENT = 0, OLD = 1, TILED = 2 };
+        auto step = [&](int how, int st, float* th, unsigned char* wpo, float lr) {
+          void* wp_arg = st == STEPS - 1 ? nullptr : (void*)wpo;
+          if (how == TILED)
+            return bwdt(ktp, ktp_rt, ktp_kt, dzps[st], dzp_rt, dzp_kt, alpha, th, mask, S, N, B, in_dim, HID, ldp, lr, wp_arg, wp_rt, wp_kt, wt,
+                        wt_bytes, st > 0, st < STEPS - 1, nullptr);
+          return (how == PARENT ? bwdp : bwd0)(ktp, ktp_rt, ktp_kt, dzps[st], dzp_rt, dzp_kt, alpha, th, mask, S, N, B, in_dim, HID, ldp, lr,
+                                               wp_arg, wp_rt, wp_kt, nullptr);
+        };
+        // ---- word compare: theta / wp_out run the tiled roles, theta_ref / wp_ref the strided entry point
+        CK(hipMemcpy(theta, theta0, n_th * 4, hipMemcpyDeviceToDevice));
+        CK(hipMemcpy(theta_ref, theta0, n_th * 4, hipMemcpyDeviceToDevice));
+        CK(hipMemset(wp_out, 0, wp_b)); CK(hipMemset(wp_ref, 0, wp_b));
+        long bad = 0;
+        for (int st = 0; st < STEPS; ++st) {
+          rc |= step(OLD, st, theta_ref, wp_ref, 0.01f);
+          rc |= step(TILED, st, theta, wp_out, 0.01f);
+          CK(hipDeviceSynchronize());
+          const long nd = ndiff(wp_out, wp_ref, wp_b, d_count);
+          printf("seq in=%4d %-40s step %d rc=%d diff wp=%ld\n", in_dim, argv[ci], st, rc, nd);
+          bad += nd;
+        }
+        const long ndt = ndiff(theta, theta_ref, n_th * 4, d_count), moved = ndiff(theta, theta0, n_th * 4, d_count);
+        printf("seq in=%4d %-40s after the last step: diff theta=%ld (words changed by the fit: %ld)\n", in_dim, argv[ci], ndt, moved);
+        bad += ndt;
+        if (bad || !moved || rc) { fprintf(stderr, "seq: MISMATCH\n"); return 3; }
+        // ---- time per launch by role
+        std::vector<hipEvent_t> ev(2 * STEPS * iters);
+        for (auto& e : ev) CK(hipEventCreate(&e));
+        const char* names[3] = {"parent strided", "this   strided", "this   tiled  "};
+        for (int r = 0; r < reps; ++r)
+          for (int how = bwdp ? PARENT : OLD; how <= TILED; ++how) {
+            CK(hipMemcpy(theta, theta0, n_th * 4, hipMemcpyDeviceToDevice));
+            for (int st = 0; st < STEPS; ++st) step(how, st, theta, wp_out, 1e-9f);          // warm-up fit
+            for (int i = 0; i < iters; ++i)
+              for (int st = 0; st < STEPS; ++st) {
+                CK(hipEventRecord(ev[2 * (i * STEPS + st)], 0));
+                step(how, st, theta, wp_out, 1e-9f);
+                CK(hipEventRecord(ev[2 * (i * STEPS + st) + 1], 0));
+              }
+            CK(hipDeviceSynchronize());
+            double us[STEPS] = {0};
+            for (int i = 0; i < iters; ++i)
+              for (int st = 0; st < STEPS; ++st) {
+                float ms = 0;
+                CK(hipEventElapsedTime(&ms, ev[2 * (i * STEPS + st)], ev[2 * (i * STEPS + st) + 1]));
+                us[st] += ms * 1e3 / iters;
+              }
+            printf("seq in=%4d %-40s rep %d %s us/launch: first %7.1f  middle %7.1f %7.1f %7.1f (mean %7.1f)  last %7.1f  fit %8.1f\n", in_dim,
+                   argv[ci], r, names[how], us[0], us[1], us[2], us[3], (us[1] + us[2] + us[3]) / 3, us[4],
+                   us[0] + us[1] + us[2] + us[3] + us[4]);
+            fflush(stdout);
+          }
+        for (auto& e : ev) hipEventDestroy(e);
+        for (int st = 0; st < STEPS; ++st) hipFree(dzps[st]);
+        hipFree(wt);
+        if (hp) dlclose(hp);
+        for (auto& p : kv) unsetenv(p.first.c_str());
+      }
+    }
+    for (int ci = 3; ci < argc && what != "seq"; ++ci) {
       const auto kv = parse_cfg(argv[ci]);
       for (auto& p : kv) setenv(p.first.c_str(), p.second.c_str(), 1);
-      fwd_t fwd = fwd0; bwd_t bwd = bwd0; bwdws_t bwdws = bwdws0;
+      fwd_t fwd = fwd0; bwd_t bwd = bwd0;
       void* hv = nullptr;
       if (getenv("LIB")) {                                    // a variant build of the library for this configuration's GEMM calls
         hv = dlopen(getenv("LIB"), RTLD_NOW | RTLD_LOCAL);
         if (!hv) { fprintf(stderr, "dlopen %s: %s\n", getenv("LIB"), dlerror()); return 1; }
         fwd = (fwd_t)dlsym(hv, "rcmarl_layer1_forward_lattice");
         bwd = (bwd_t)dlsym(hv, "rcmarl_layer1_backward_sgd_lattice");
-        bwdws = (bwdws_t)dlsym(hv, "rcmarl_layer1_backward_sgd_lattice_ws");
       }
       typedef void (*tsdump_t)(const char*);
       tsdump_t tsdump = (tsdump_t)dlsym(hv ? hv : h, "rcmarl_lat_ts_dump");
-      const bool use_ws = getenv("LB_WS") && atoi(getenv("LB_WS")) && bwdws && ws;
       if (what == "fwd" || what == "both") {
         CK(hipMemset(a1t, 0xff, n_a1 * 4));
         rc = fwd(kp, kp_rt, kp_kt, wp, wp_rt, wp_kt, theta0, a1t, S, N, B, in_dim, HID, ldp, ldb, nullptr);
@@ -177,10 +265,8 @@ int main(int argc, char** argv) {
       if (what == "bwd" || what == "both") {
         void* wp_arg = (getenv("LB_NOWP") && atoi(getenv("LB_NOWP"))) ? nullptr : (void*)wp_out;      // knock-out: no next-forward operand
         auto call = [&](float lr) {
-          return use_ws ? bwdws(ktp, ktp_rt, ktp_kt, dzp, dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, HID, ldp, lr, wp_arg, wp_rt,
-                                wp_kt, ws, ws_bytes, nullptr)
-                        : bwd(ktp, ktp_rt, ktp_kt, dzp, dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, HID, ldp, lr, wp_arg, wp_rt,
-                              wp_kt, nullptr);
+          return bwd(ktp, ktp_rt, ktp_kt, dzp, dzp_rt, dzp_kt, alpha, theta, mask, S, N, B, in_dim, HID, ldp, lr, wp_arg, wp_rt, wp_kt,
+                     nullptr);
         };
         CK(hipMemcpy(theta, theta0, n_th * 4, hipMemcpyDeviceToDevice));
         CK(hipMemset(wp_out, 0, wp_b));
@@ -197,8 +283,8 @@ int main(int argc, char** argv) {
         float ms = 0;
         CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / iters;
-        printf("bwd in=%4d %-70s rc=%d %8.1f us %6.1f TF/s fp32-eq  diff theta=%ld wp=%ld%s\n", in_dim, argv[ci], rc, us, flops / us / 1e6, nd1,
-               nd2, use_ws ? " (ws)" : "");
+        printf("bwd in=%4d %-70s rc=%d %8.1f us %6.1f TF/s fp32-eq  diff theta=%ld wp=%ld\n", in_dim, argv[ci], rc, us, flops / us / 1e6, nd1,
+               nd2);
         if (tsdump) { char tag[64]; snprintf(tag, sizeof tag, "bwd in=%d cfg %d", in_dim, ci - 3); tsdump(tag); }
       }
       for (auto& p : kv) unsetenv(p.first.c_str());
@@ -207,7 +293,6 @@ int main(int argc, char** argv) {
     }
     hipFree(x); hipFree(alpha); hipFree(theta0); hipFree(theta); hipFree(theta_ref); hipFree(a1t); hipFree(a1t_ref); hipFree(dz);
     hipFree(kp); hipFree(ktp); hipFree(wp); hipFree(dzp); hipFree(wp_out); hipFree(wp_ref); hipFree(flag); hipFree(mask);
-    if (ws) hipFree(ws);
   }
   return 0;
 }
