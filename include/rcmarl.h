@@ -315,6 +315,21 @@ int rcmarl_minibatch_actor(const float* x, long x_seed_stride, float* theta, flo
                            int N, int B, int in_dim, int hid, int n_actions, int ldp, int ldb, int batch_size,
                            int epochs, double lr, double beta1, double beta2, double eps, int t0, float* loss_out,
                            void* stream);
+/* The same actor fit (agents/adversarial_CAC_agents.py:38-41,111-117,221-225: actor.fit(batch_size=200, epochs=1), Adam on the
+ * sample-weighted sparse cross-entropy) for an actor of ANY hidden width -- csrc/minibatch_actor_wide.hip: one workgroup per
+ * (seed, adversary) chain for the whole fit, fp32 on the exact-f32 matrix instruction, a mini-batch walked in 32-row tiles whose
+ * gradients are summed in `grad`, one Adam pass per mini-batch.  Arguments, layouts and semantics are those of rcmarl_minibatch_actor;
+ * grad: scratch [S][n_adv][ldp] owned by the caller (the library owns no device memory), zeroed by the kernel.  Rows of theta,
+ * adam_m, adam_v of agents not in `agents` are never written.
+ * rcmarl_minibatch_actor_wide_supported (host only): 1: this shape is served -- every hid <= 384 (three [32][hid] activation images
+ * within the 160 KiB of LDS) with 2 <= n_actions <= 8, any in_dim >= 1 and batch_size >= 1; 0 otherwise, non-positive arguments
+ * included.  An unserved shape returns RCMARL_ERR_UNSUPPORTED, bad pointers or sizes (ldp no multiple of 64, a net that does not fit
+ * its row, ldb < B, grad == NULL) RCMARL_ERR_ARG, both before the HIP runtime is touched. */
+int rcmarl_minibatch_actor_wide_supported(int in_dim, int hid, int n_actions, int batch_size);
+int rcmarl_minibatch_actor_wide(const float* x, long x_seed_stride, float* theta, float* adam_m, float* adam_v, float* grad,
+                                const int* agents, int n_adv, const float* act_t, const float* delta, const int* perm, int S,
+                                int N, int B, int in_dim, int hid, int n_actions, int ldp, int ldb, int batch_size, int epochs,
+                                double lr, double beta1, double beta2, double eps, int t0, float* loss_out, void* stream);
 
 /* r_coop[s][b] = sum_{coop n, index order} r[s][b][n]/n_coop   (training/train_agents.py:96-98) */
 int rcmarl_team_reward(const float* r, long seed_stride, const int* coop, int n_coop, float* rcoop, int S,

@@ -3,7 +3,10 @@ message generators the resilient consensus must withstand.
 
 Same constructors and methods as the reference (Faulty :19-73, Malicious :90-182,
 Greedy :200-275).  Keras' shuffled mini-batch ``fit`` calls are single kernel
-launches (csrc/minibatch_fit.hip).  The shuffle permutations come from a
+launches (csrc/minibatch_fit.hip for 20-unit models; csrc/minibatch_wide*.hip and
+csrc/minibatch_actor_wide.hip for models of another hidden width, which
+single.RowOps reads off the weights -- the Malicious agent's private critic list
+included).  The shuffle permutations come from a
 process-wide stream (``set_shuffle_seed``): epoch e of the n-th mini-batch fit of a run visits
 the rows in the order that sorts Philox(counter=(row, e, n, 2), key=seed) (csrc/shuffle.hip) -- a
 definition, shared with the oracle, since TensorFlow's own shuffle RNG cannot be reproduced

@@ -13,7 +13,9 @@ the C-ABI kernels (rcmarl_amd.single.RowOps) instead of TensorFlow/Keras:
 
 The models (``actor``, ``critic``, ``team_reward``) are rcmarl_amd.keras_compat
 objects or anything exposing ``get_weights/set_weights/output_shape`` with the
-architecture of main.py:59-82.  ``train_RPBCAC`` does NOT call these methods in
+architecture of main.py:59-82 at any hidden width (two equal LeakyReLU(0.1) hidden
+layers; 20 units run on the 20-unit kernels, any other width on the dense fp32
+entry points).  ``train_RPBCAC`` does NOT call these methods in
 a loop: it batches all agents into one engine.  They exist so that code written
 against the reference's per-agent API keeps working.
 """

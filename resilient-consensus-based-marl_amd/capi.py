@@ -134,6 +134,13 @@ SIGNATURES = {
     "rcmarl_minibatch_actor": [c_f32p, c_long, c_f32p, c_f32p, c_f32p, c_i32p, c_int, c_f32p, c_f32p, c_i32p, c_int,
                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double,
                                C.c_double, C.c_double, c_int, c_f32p, c_stream],
+    # the same fit for an actor of any hidden width (csrc/minibatch_actor_wide.hip): in_dim, hid, n_actions, batch_size
+    "rcmarl_minibatch_actor_wide_supported": [c_int, c_int, c_int, c_int],
+    # x, x_seed_stride, theta, adam_m, adam_v, grad (scratch [S][n_adv][ldp]), agents, n_adv, act_t, delta, perm, S, N, B, in_dim, hid,
+    # n_actions, ldp, ldb, batch_size, epochs, lr, beta1, beta2, eps, t0, loss_out, stream
+    "rcmarl_minibatch_actor_wide": [c_f32p, c_long, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_int, c_f32p, c_f32p, c_i32p, c_int,
+                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double,
+                                    C.c_double, C.c_double, c_int, c_f32p, c_stream],
     # src, seed_stride, rcoop, mode, out, S, N, B, ldb, stream
     "rcmarl_gather_agent_major": [c_f32p, c_long, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_stream],
     # src, seed_stride, first, step, n_rows, width, dst, S, stream
@@ -258,7 +265,7 @@ UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_
              "rcmarl_wide_grad_size", "rcmarl_wide_rows_per_chunk", "rcmarl_wide_f16_mode", "rcmarl_wide_set_f16_mode",
              "rcmarl_consensus_params_circulant_supported", "rcmarl_pk_supported", "rcmarl_pk_parts",
              "rcmarl_rollout_wide_supported", "rcmarl_minibatch_fit_wide_supported",
-             "rcmarl_minibatch_fit_wide2_supported"}
+             "rcmarl_minibatch_fit_wide2_supported", "rcmarl_minibatch_actor_wide_supported"}
 
 # host-only size queries that return long (bytes), not a status: name -> argtypes
 LONG_QUERIES = {

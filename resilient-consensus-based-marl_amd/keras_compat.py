@@ -74,9 +74,9 @@ class Sequential:
         dense = [l for l in self.layers if isinstance(l, Dense)]
         if len(inp) != 1 or len(dense) != 3:
             raise ValueError("expected Input, Flatten and three Dense layers (main.py:59-82)")
-        # two equally wide LeakyReLU(0.1) hidden layers.  20 units (main.py:59-82) run everywhere; other widths are for
-        # critics and actors trained through train_RPBCAC (dense-GEMM paths of the engine) -- the per-agent method views
-        # (model(x), fit, ...) are compiled for 20 units and raise RcmarlError(UNSUPPORTED) otherwise
+        # two equally wide LeakyReLU(0.1) hidden layers.  20 units (main.py:59-82) run on the 20-unit kernels; any other width
+        # runs on the dense-GEMM paths, in train_RPBCAC's engine and in the per-agent method views (model(x), predict, the agent
+        # classes' fits: single.RowOps) alike
         for l in dense[:2]:
             if not isinstance(l.activation, LeakyReLU) or abs(l.activation.alpha - 0.1) > 1e-12 or l.units != dense[0].units:
                 raise ValueError("hidden layers must be two Dense(h, LeakyReLU(alpha=0.1)) of equal width h")

@@ -8,6 +8,7 @@
     python tools/kbench.py rollout_wide  # wide actor: one step of 50 episodes, matrix-core kernel vs plain kernel vs the weight stream
     python tools/kbench.py mb_wide [--hid 64] [--in-dim I --chains 2,8,64,256]   # adversaries beside wide nets: one mini-batch-fit launch
                                      # (the entry point the library's queries name for the width) vs the eight launches per step
+    python tools/kbench.py mb_actor_wide # adversaries' actor fit of a wide actor: one launch vs the nine-launch Adam step per mini-batch
 """
 import os
 import sys
@@ -692,8 +693,58 @@ def mb_wide(L, N=5, B=2000, epochs=10, bs=32):
               "and chain; %.0f x the loop" % (S, entry, 3 * S, t, t / steps, t / steps / (3 * S), loop / t))
 
 
+def mb_actor_wide(L, N=16, B=1000, bs=200, in_dim=10, A=5, lr=0.002):
+    """The adversaries' actor fit(batch_size=200, epochs=1) of a wide actor: ONE rcmarl_minibatch_actor_wide launch over all chains
+    against the nine launches of the wide Adam step (engine._actor_step_wide) once per mini-batch on 200 gathered rows of a
+    (seed, agent) = (1, 1) view, chain after chain; hid 64 and 384, 1 and 16 chains (adversaries of one seed).
+
+        python tools/kbench.py mb_actor_wide"""
+    st = torch.cuda.current_stream().cuda_stream
+    steps, ldb, ldn = (B + bs - 1) // bs, pad64(B), pad64(bs)
+    p = lambda t: t.data_ptr()
+    z = lambda *s: torch.zeros(*s, device="cuda")
+    for hid in (64, 384):
+        o_b1 = in_dim * hid
+        o_W2 = o_b1 + hid
+        o_b2 = o_W2 + hid * hid
+        o_W3 = o_b2 + hid
+        ldp = pad64(o_W3 + hid * A + A)
+        assert L.rcmarl_minibatch_actor_wide_supported(in_dim, hid, A, bs) == 1
+        # the yardstick: one mini-batch step of one chain
+        th, m, v = torch.empty(1, 1, ldp, device="cuda").uniform_(-0.1, 0.1), z(1, 1, ldp), z(1, 1, ldp)
+        xb, act, dl = torch.randn(bs, in_dim, device="cuda"), torch.randint(0, A, (1, 1, ldn), device="cuda").float(), torch.randn(1, 1, ldn, device="cuda")
+        a1, a2, dz, dz3, lp, loss = z(hid, ldn), z(hid, ldn), z(hid, ldn), z(A, ldn), z(4), z(1, 1)
+        adam = (float(np.float32(lr)), float(np.float32(0.1)), float(np.float32(0.001)), float(np.float32(1e-7)), st)
+
+        def step():
+            L.rcmarl_dense_forward(p(xb), 0, 0, 1, in_dim, p(th), 0, o_b1, p(a1), 1, 1, bs, in_dim, hid, ldp, ldn, st)
+            L.rcmarl_dense_forward(p(a1), hid * ldn, hid * ldn, 0, ldn, p(th), o_W2, o_b2, p(a2), 1, 1, bs, hid, hid, ldp, ldn, st)
+            L.rcmarl_wide_actor_head(p(a2), p(th), p(act), p(dl), ldn, p(dz3), p(lp), 1, 1, bs, in_dim, hid, A, ldp, ldn, st)
+            L.rcmarl_dense_backward_data(p(dz3), p(th), o_W3, p(a2), p(dz), 1, 1, bs, hid, A, ldp, ldn, st)
+            L.rcmarl_dense_backward_adam(p(a2), hid * ldn, hid * ldn, 0, ldn, p(dz3), p(th), p(m), p(v), o_W3, None, 1, 1, bs, hid, A, ldp, ldn, *adam)
+            L.rcmarl_dense_backward_data(p(dz), p(th), o_W2, p(a1), p(a2), 1, 1, bs, hid, hid, ldp, ldn, st)
+            L.rcmarl_dense_backward_adam(p(a1), hid * ldn, hid * ldn, 0, ldn, p(dz), p(th), p(m), p(v), o_W2, None, 1, 1, bs, hid, hid, ldp, ldn, *adam)
+            L.rcmarl_dense_backward_adam(p(xb), 0, 0, 1, in_dim, p(a2), p(th), p(m), p(v), 0, None, 1, 1, bs, in_dim, hid, ldp, ldn, *adam)
+            L.rcmarl_wide_actor_small_adam(p(a2), p(dz), p(dz3), p(lp), p(th), p(m), p(v), None, p(loss), 1, 1, bs, in_dim, hid, A, ldp, ldn, *adam)
+        t_step = timeit(step, iters=200, warm=20)
+        print("nine-launch composition, in=%d hid=%d: %7.1f us per mini-batch step of %d rows" % (in_dim, hid, t_step, bs), flush=True)
+        x = torch.randn(1, B, in_dim, device="cuda")
+        for chains in (1, 16):
+            assert chains <= N
+            theta, mm, vv, grad = torch.empty(1, N, ldp, device="cuda").uniform_(-0.1, 0.1), z(1, N, ldp), z(1, N, ldp), z(1, chains, ldp)
+            acts, delta = torch.randint(0, A, (1, N, ldb), device="cuda").float(), torch.randn(1, N, ldb, device="cuda")
+            agents = torch.arange(chains, dtype=torch.int32, device="cuda")
+            perm = torch.stack([torch.randperm(B, device="cuda") for _ in range(chains)]).to(torch.int32).reshape(1, chains, 1, B).contiguous()
+            t = timeit(lambda: L.rcmarl_minibatch_actor_wide(p(x), B * in_dim, p(theta), p(mm), p(vv), p(grad), p(agents), chains, p(acts),
+                                                             p(delta), p(perm), 1, N, B, in_dim, hid, A, ldp, ldb, bs, 1, lr, 0.9, 0.999, 1e-7,
+                                                             0, None, st), iters=20, warm=3)
+            loop = t_step * steps * chains
+            print("hid=%3d %2d chains x %d steps: ONE rcmarl_minibatch_actor_wide launch %9.1f us; the composition's %d x %d steps %9.1f us; "
+                  "composition / launch = %.2f" % (hid, chains, steps, t, chains, steps, loop, loop / t), flush=True)
+
+
 if __name__ == "__main__":
     L = capi.CLib(os.environ["RCMARL_KBENCH_LIB"]) if os.environ.get("RCMARL_KBENCH_LIB") else capi.load()     # (variant builds)
     what = sys.argv[1] if len(sys.argv) > 1 else "gemm"
     print("== %s  RCMARL_GEMM=%s RCMARL_K1=%s" % (what, os.environ.get("RCMARL_GEMM"), os.environ.get("RCMARL_K1")))
-    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk, "rollout_wide": rollout_wide, "mb_wide": mb_wide}[what](L)
+    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk, "rollout_wide": rollout_wide, "mb_wide": mb_wide, "mb_actor_wide": mb_actor_wide}[what](L)
