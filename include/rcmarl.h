@@ -205,6 +205,13 @@ int rcmarl_shuffle_perms(const void* seeds, const int* calls, int n, int epochs,
 /* reduce the partials over chunks and apply SGD to b1,W2,b2,W3,b3; loss_out[S][N] (or NULL) = MSE. */
 int rcmarl_small_sgd(const float* partials, float* theta, const int* mask, float* loss_out, int S, int N,
                      int B, int in_dim, int hid, int ldp, float lr, void* stream);
+/* The same step with a separate source: dst(b1,W2,b2,W3,b3) = src(...) - lr * sum of the partials, same summation order, so
+ * rcmarl_small_sgd(p, theta, ...) IS rcmarl_small_sgd_from(p, theta, theta, ...).  Rows of dst whose agent is masked, and every word
+ * of dst outside the five small arrays (W1, the columns P..ldp), are not written; src is only read.  For the first step of a local
+ * fit that starts from the live net and writes the message (no copy of the net in front of the fit).  NULL src or dst:
+ * RCMARL_ERR_ARG.  (Added without an ABI bump, like the ABI-4 additions before it.) */
+int rcmarl_small_sgd_from(const float* partials, const float* src, float* dst, const int* mask, float* loss_out, int S, int N,
+                          int B, int in_dim, int hid, int ldp, float lr, void* stream);
 /* K6: out[s][n][b] = head(a1t) (r_applied NULL), or the TD target r_applied + gamma*V
  * (local_TD_target, agents/resilient_CAC_agents.py:114-115).  Also serves r_team, V, nV of :95-97. */
 int rcmarl_mid_value(const float* a1t, const float* theta, const float* r_applied, float gamma, float* out, int S,

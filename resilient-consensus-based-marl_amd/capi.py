@@ -104,6 +104,8 @@ SIGNATURES = {
     "rcmarl_shuffle_perms": [C.c_void_p, c_i32p, c_int, c_int, c_int, c_i32p, c_int, c_stream],
     # partials, theta, mask, loss_out, S, N, B, in_dim, hid, ldp, lr, stream
     "rcmarl_small_sgd": [c_f32p, c_f32p, c_u8p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_stream],
+    # partials, src, dst, mask, loss_out, S, N, B, in_dim, hid, ldp, lr, stream
+    "rcmarl_small_sgd_from": [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_stream],
     # a1t, theta, r_applied, gamma, out, S, N, B, in_dim, hid, ldp, ldb, stream
     "rcmarl_mid_value": [c_f32p, c_f32p, c_f32p, c_float, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                          c_stream],

@@ -249,7 +249,11 @@ void k_lat_forward(const unsigned char* __restrict__ wp, int wp_rt, int wp_kt, c
   op.a = wp + (long)s * wp_rt * wp_kt * (PA * RC_PK_BLOCK); op.a_kt = wp_kt; op.art0 = bm * C::ART;
   op.b = kp + (long)s * kp_rt * kp_kt * (PB * RC_PK_BLOCK); op.b_kt = kp_kt; op.brt0 = bn * C::BRT;
   rc_f32x16 acc[MT][NT];
-  lat_mainloop<PA, PB, MT, NT, WM, WN, false, F16>(op, (in_dim + 31) >> 5, lds, acc);
+  // The last row tile of a B that is no multiple of BN: a wavefront whose first replay row lies beyond B would multiply nothing but
+  // padding (its stores below are predicated off by n < B) -- B = 3000: the two wavefronts with wn == 3 of the twelfth tile.  Not in
+  // the packed form, which writes the rows beyond B on purpose.
+  const bool dead = !PK && bn * C::BN + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) % WN * (32 * NT) >= B;
+  lat_mainloop<PA, PB, MT, NT, WM, WN, false, F16, false, !PK>(op, (in_dim + 31) >> 5, lds, acc, dead);
   // epilogue: a1t[col][b] = lrelu(z + b1[col])
   const int ncols = N * hid;
   const float* theta_s = theta + (long)s * N * ldp;

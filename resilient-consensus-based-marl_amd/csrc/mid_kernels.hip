@@ -724,9 +724,10 @@ __global__ __launch_bounds__(256, kV8Waves) void k_mid_fit_v8(float* __restrict_
   }
 }
 
-// theta(small arrays) -= lr * sum_chunks partial; optional loss_out[s][n] = sum(diff^2)/B.
+// dst(small arrays) = src(small arrays) - lr * sum_chunks partial; optional loss_out[s][n] = sum(diff^2)/B.
+// src == dst is the in-place step (no __restrict__ on the two: they may be the same rows); a masked agent's dst row is not touched.
 template <int HID>
-__global__ __launch_bounds__(256) void k_small_sgd(const float* __restrict__ partials, float* __restrict__ theta,
+__global__ __launch_bounds__(256) void k_small_sgd(const float* __restrict__ partials, const float* src, float* dst,
                                                    const int* __restrict__ mask,
                                                    float* __restrict__ loss_out, int N, int B, int in_dim, int ldp,
                                                    int nchunk, float lr) {
@@ -734,7 +735,8 @@ __global__ __launch_bounds__(256) void k_small_sgd(const float* __restrict__ par
   const int s = blockIdx.y, i = blockIdx.x;
   if (mask && !mask[i]) return;
   const NetGeom g = make_geom(in_dim, HID, 1);
-  float* th = theta + ((long)s * N + i) * ldp;
+  const float* th0 = src + ((long)s * N + i) * ldp;
+  float* th = dst + ((long)s * N + i) * ldp;
   const float* pp = partials + ((long)s * N + i) * nchunk * PT::SIZE;
   for (int e = threadIdx.x; e < PT::SIZE; e += blockDim.x) {
     float sum = 0.f;
@@ -749,7 +751,7 @@ __global__ __launch_bounds__(256) void k_small_sgd(const float* __restrict__ par
     else if (e < PT::gb3) o = g.o_W3 + (e - PT::gW3);
     else if (e < PT::gb1) o = g.o_b3;
     else o = g.o_b1 + (e - PT::gb1);
-    th[o] = th[o] - lr * sum;
+    th[o] = th0[o] - lr * sum;
   }
 }
 
@@ -1641,14 +1643,19 @@ RCMARL_EXPORT int rcmarl_mid_fit_lattice(const float* a1t, const float* theta, c
   return rcmarl_check_launch();
 }
 
-RCMARL_EXPORT int rcmarl_small_sgd(const float* partials, float* theta, const int* mask, float* loss_out,
-                                   int S, int N, int B, int in_dim, int hid, int ldp, float lr, void* stream) {
-  if (!partials || !theta || S <= 0 || N <= 0 || B <= 0) return RCMARL_ERR_ARG;
+RCMARL_EXPORT int rcmarl_small_sgd_from(const float* partials, const float* src, float* dst, const int* mask, float* loss_out,
+                                        int S, int N, int B, int in_dim, int hid, int ldp, float lr, void* stream) {
+  if (!partials || !src || !dst || S <= 0 || N <= 0 || B <= 0) return RCMARL_ERR_ARG;
   const int nchunk = rc_ceil_div(B, ROWS), nrec = rc_ceil_div(nchunk, midfit_cpw(nchunk, (long)S * N));   // = rcmarl_mid_fit's grid
   const dim3 grid(N, S), block(256);
-  RC_HID_SWITCH(hid, RCMARL_LAUNCH((k_small_sgd<HID_>), grid, block, 0, stream, partials, theta, mask, loss_out, N, B,
+  RC_HID_SWITCH(hid, RCMARL_LAUNCH((k_small_sgd<HID_>), grid, block, 0, stream, partials, src, dst, mask, loss_out, N, B,
                                    in_dim, ldp, nrec, lr));
   return rcmarl_check_launch();
+}
+
+RCMARL_EXPORT int rcmarl_small_sgd(const float* partials, float* theta, const int* mask, float* loss_out,
+                                   int S, int N, int B, int in_dim, int hid, int ldp, float lr, void* stream) {
+  return rcmarl_small_sgd_from(partials, theta, theta, mask, loss_out, S, N, B, in_dim, hid, ldp, lr, stream);
 }
 
 static int mid_value_impl(const float* a1t, const float* theta, const float* r_applied, float gamma, float* out, int S, int N, int B,

@@ -39,9 +39,12 @@ struct LatOperands {
 // the next stage BEHIND its matrix work instead of in front of it +5..+9 %, static priority for that half +4..+6 %.)
 // DROP_LL (dense_pk.hip: both operands fp32-valued, two f16 pieces each): the product of the two LOW pieces (2^-22 of the result) is
 // not formed -- three matrix passes per fp32 product instead of four.
-template <int PA, int PB, int MT, int NT, int WM, int WN, bool SPREAD, bool F16, bool DROP_LL = false>
+// SKIP_DEAD (k_lat_forward's fp32-activation form): a wavefront the caller declares `dead` (wave-uniform: all of its B-side rows lie
+// beyond the problem, its accumulators are never stored) reads no fragments and issues no matrix instructions; it still fetches its
+// share of every stage, waits for it and joins every barrier, so its live neighbours see the k-loop they always saw.
+template <int PA, int PB, int MT, int NT, int WM, int WN, bool SPREAD, bool F16, bool DROP_LL = false, bool SKIP_DEAD = false>
 __device__ __forceinline__ void lat_mainloop(const LatOperands& op, int n_ktiles, unsigned char* lds,
-                                             rc_f32x16 (&acc)[MT][NT]) {
+                                             rc_f32x16 (&acc)[MT][NT], bool dead = false) {
   typedef LatCfg<PA, PB, MT, NT, WM, WN> C;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -85,6 +88,7 @@ __device__ __forceinline__ void lat_mainloop(const LatOperands& op, int n_ktiles
   constexpr int N_MFMA = 2 * PA * PB * MT * NT;                 // matrix-core instructions of a wavefront per k-tile
   constexpr int EVERY = (N_MFMA / 2) / C::GLDS > 0 ? (N_MFMA / 2) / C::GLDS : 1;     // all bursts within the first half
   static_assert(!SPREAD || EVERY * C::GLDS <= N_MFMA, "spread issue: every burst has a slot");
+  static_assert(!SKIP_DEAD || !SPREAD, "a dead wavefront's bursts are not tied to its matrix instructions");
 
   // fragment addresses: row = lane&31 (+ tile offsets), chunk = 2*kstep + lane>>5, XOR (row>>2)&3
   const int sw = (l31 >> 2) & 3;
@@ -108,6 +112,7 @@ __device__ __forceinline__ void lat_mainloop(const LatOperands& op, int n_ktiles
     __syncthreads();                // ... and everybody's; all reads of the buffer refilled next are done
     const bool more = t + 1 < n_ktiles;
     if (more && !SPREAD) stage(cur ^ 1, t + 1);
+    if (SKIP_DEAD && dead) continue;
     const unsigned char* st = lds + cur * C::STAGE_BYTES;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {

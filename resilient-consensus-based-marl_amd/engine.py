@@ -28,6 +28,8 @@ HID = 20
 COOP, FAULTY, GREEDY, MALICIOUS = "Cooperative", "Faulty", "Greedy", "Malicious"
 # EngineConfig(w1_tiled="auto"): what the measurement of docs/history/r12.md decided
 W1_TILED_AUTO = True
+# EngineConfig(fit_from_live="auto"): step 0 of a local fit reads the live net, no copy of it in front (docs/history/r14.md)
+FIT_FROM_LIVE_AUTO = True
 
 
 def pad64(n):
@@ -68,7 +70,7 @@ class EngineConfig:
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
                  local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID, adv_wide2="auto",
-                 w1_tiled="auto"):
+                 w1_tiled="auto", fit_from_live="auto"):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -98,6 +100,11 @@ class EngineConfig:
         if not any(w1_tiled is v for v in (True, False)) and w1_tiled != "auto":
             raise ValueError("w1_tiled must be 'auto', True or False")
         self.w1_tiled = w1_tiled
+        # the same fits, all-cooperative team: step 0 reads the live net and writes the message, so the epoch does not copy the net
+        # into the message first (RPBCACEngine._fit_from_live has the rule): "auto" (see FIT_FROM_LIVE_AUTO) | True | False
+        if not any(fit_from_live is v for v in (True, False)) and fit_from_live != "auto":
+            raise ValueError("fit_from_live must be 'auto', True or False")
+        self.fit_from_live = fit_from_live
         assert len(self.agent_label) == self.n_agents and len(self.in_nodes) == self.n_agents
         if np.ndim(H) == 0:
             self.H_per_agent = [int(H)] * self.n_agents
@@ -1181,25 +1188,43 @@ class RPBCACEngine:
         dzp, wp = (self.lat_dzp_f[xkey], self.lat_wp_f[xkey]) if lat else (None, None)
         partials = self.partials if partials is None else partials
         wp_fresh = False
+        # Fit from the live net (_fit_from_live: _epoch_body has NOT copied theta into msg): step 0 reads theta wherever it would read
+        # the copy, and the message is complete when the fit ends, because for every fitted agent (here: every agent)
+        #   - rcmarl_small_sgd_from writes every element of b1, W2, b2, W3, b3 of its msg row at step 0 (k_small_sgd walks the whole
+        #     partial record; only the loss entry is not a parameter), and steps 1.. update those in place;
+        #   - the strided -> tiled launch of step 0 reads W1 from theta and writes only the tiled scratch and Wp (ROLE 2 of
+        #     k_lat_backward_sgd has no strided store); the last step (tiled -> strided) writes every W1[k][col] with k < in_dim of
+        #     an unmasked agent, i.e. all of W1;
+        #   - between the two nothing reads the fp32 W1 of msg: the forward of steps 1.. reads Wp and b1 (small array, written at
+        #     step 0), the mid step and the small step read the small arrays;
+        #   - afterwards K1 reads columns < P_hid and K2 reads W3, b3 of msg: all written.  The columns P..ldp of a row are read by
+        #     nobody and are zero in theta and msg alike (no kernel writes them).
+        live = self._fit_from_live(net, xkey, B, mask)
         for step in range(self.cfg.local_fit_steps):
+            src = self.theta[net] if live and step == 0 else msg
             if not (step == 0 and self.a1_cached[net]):       # msg == live net: activations left by _consensus
-                self._layer1(xkey, msg, net, B, buf=a1, wp_fresh=wp_fresh)
+                self._layer1(xkey, src, net, B, buf=a1, wp_fresh=wp_fresh)
             if lat:
-                L.rcmarl_mid_fit_lattice(a1.data_ptr(), msg.data_ptr(), y.data_ptr(), partials.data_ptr(),
+                L.rcmarl_mid_fit_lattice(a1.data_ptr(), src.data_ptr(), y.data_ptr(), partials.data_ptr(),
                                          dzp.data_ptr(), g.dzp[0], g.dzp[1], S, N, B, self.in_dim[net], HID,
                                          self.ldp[net], self.ldb, self.ovf_flags(("mid", net), S * N + 1).data_ptr(), self.stream)
             else:
                 L.rcmarl_mid_fit(a1.data_ptr(), msg.data_ptr(), y.data_ptr(), partials.data_ptr(), S, N, B,
                                  self.in_dim[net], HID, self.ldp[net], self.ldb, self.stream)
-            L.rcmarl_small_sgd(partials.data_ptr(), msg.data_ptr(), mask.data_ptr(),
-                               self.loss[net].data_ptr() if step == 0 else None, S, N, B, self.in_dim[net], HID,
-                               self.ldp[net], self.cfg.fast_lr, self.stream)
+            if src is msg:
+                L.rcmarl_small_sgd(partials.data_ptr(), msg.data_ptr(), mask.data_ptr(),
+                                   self.loss[net].data_ptr() if step == 0 else None, S, N, B, self.in_dim[net], HID,
+                                   self.ldp[net], self.cfg.fast_lr, self.stream)
+            else:
+                L.rcmarl_small_sgd_from(partials.data_ptr(), src.data_ptr(), msg.data_ptr(), mask.data_ptr(),
+                                        self.loss[net].data_ptr(), S, N, B, self.in_dim[net], HID, self.ldp[net],
+                                        self.cfg.fast_lr, self.stream)
             if lat:
                 # the epilogue also leaves the bf16x3 split of the updated W1 for the NEXT step's forward -- except after
                 # the last step, whose weights only travel as a message (252 / 378 MB of writes per fit at cfg 4)
                 last = step == self.cfg.local_fit_steps - 1
                 args = (self.lat_ktp[xkey].data_ptr(), g.ktp[0], g.ktp[1], dzp.data_ptr(), g.dzp[0], g.dzp[1],
-                        self.lat_alpha[xkey].data_ptr(), msg.data_ptr(), mask.data_ptr(), S, N, B, self.in_dim[net], HID,
+                        self.lat_alpha[xkey].data_ptr(), src.data_ptr(), mask.data_ptr(), S, N, B, self.in_dim[net], HID,
                         self.ldp[net], self.cfg.fast_lr, None if last else wp.data_ptr(), g.wp[0], g.wp[1])
                 wt = self.lat_w1_tiled
                 if wt is not None and self.cfg.local_fit_steps >= 2:
@@ -1214,6 +1239,19 @@ class RPBCACEngine:
                 L.rcmarl_layer1_backward_sgd(ptr, stride, a1.data_ptr(), msg.data_ptr(), mask.data_ptr(), S, N, B,
                                              self.in_dim[net], HID, self.ldp[net], self.ldb, self.cfg.fast_lr, self.stream)
         self.a1_cached[net] = False
+
+    def _fit_from_live(self, net, xkey, B, mask):
+        """Does the local fit of `net` start from the live net, with no copy of it into the message in front?  Asked by _epoch_body
+        (which then skips the copy) and by _local_fit (whose step 0 then reads theta): a 20-unit net on the lattice path whose fp32 W1
+        lives in the tiled scratch between the steps, so that no kernel of the fit reads W1 of msg before the last step has written
+        it; and an all-cooperative team fitted under the cooperative mask, because the rows of msg that nobody fits (adversaries,
+        masked agents) get their values from that copy.  Never an agent-sharded instance or the chain path."""
+        want = FIT_FROM_LIVE_AUTO if self.cfg.fit_from_live == "auto" else self.cfg.fit_from_live
+        return bool(want and self.hid[net] == HID and self.shard is None and not self._windowed
+                    and mask is self.coop and self.n_coop == self.N
+                    and getattr(self, "lat_enabled", False) and self._lattice_ok(xkey, B, 0) and xkey in self.lat_ktp
+                    and self.lat_w1_tiled is not None and self.cfg.local_fit_steps >= 2
+                    and not self._fit_as_chains(net, mask))
 
     def ovf_flags(self, key, n):
         """Out-of-range flag buffer of one call site (int32, zero at first use; the library's f16 kernels flag an agent / network
@@ -1283,12 +1321,24 @@ class RPBCACEngine:
                                       self.coop.data_ptr(), self.S, self.N, self.ldp[net], g_hid, c.d, c.H, None, None,
                                       self.stream)
 
-    def _cached_rows_ok(self, net, row0, nrows):
+    def _cached_rows_ok(self, net, row0, nrows, cached=None):
         """May values of `net` on replay rows row0..row0+nrows come from the activations the consensus step left in
-        a1net[net]?  (live net unchanged since, rows are whole episodes of ours, 20-unit net)"""
+        a1net[net]?  (live net unchanged since, rows are whole episodes of ours, 20-unit net)
+        cached: the answer for a caller that is about to put the activations there itself (default: are they there?)"""
         ep = self.cfg.max_ep_len
-        return (self.td_shortcut and self.a1_cached[net] and self.rows_episode_aligned and self.hid[net] == HID and ep >= 2
+        cached = self.a1_cached[net] if cached is None else cached
+        return (self.td_shortcut and cached and self.rows_episode_aligned and self.hid[net] == HID and ep >= 2
                 and row0 % ep == 0 and nrows % ep == 0)
+
+    td_from_fit_forward = True      # (False: the first epoch's TD target keeps its own forward pass over the ns rows)
+
+    def _td_from_fit_forward(self, B):
+        """First epoch of a block: does _cached_rows_ok("critic", 0, B) fail ONLY because nothing is cached yet?  Then _epoch_body
+        runs the forward pass that opens the critic's local fit ahead of the TD target (20-unit critic on the lattice path, one
+        instance on one GPU: the case _value_next_cached serves from the lattice operands)."""
+        return bool(self.td_from_fit_forward and self.reuse_activations and not self.a1_cached["critic"] and self.shard is None
+                    and getattr(self, "lat_enabled", False) and self._lattice_ok("s", B, 0) and "s" in self.lat_ktp
+                    and self._cached_rows_ok("critic", 0, B, cached=True))
 
     def _value_cached(self, net, out, row0, nrows, r_applied=None):
         """out[:, :, 0:nrows] = head(a1net[net][:, :, row0:row0+nrows])  [r_applied + gamma * that]"""
@@ -1442,12 +1492,23 @@ class RPBCACEngine:
     def _epoch_body(self, B, t0):
         """One update epoch: I) local fits of the TR and critic messages, II) resilient consensus."""
         # I) local fits of TR and critic on a copy (= the transmitted message); live nets untouched
+        # (a fit that starts from the live net -- _fit_from_live -- needs no copy: its step 0 reads theta and writes msg; at cfg 4 the
+        # two copies are 176 + 260 MB read and written again per epoch)
+        live = {"tr": self._fit_from_live("tr", "sa", B, self.coop), "critic": self._fit_from_live("critic", "s", B, self.coop)}
         if self.shard is not None and not self.shard.shard_tr:
             self.msg["tr"].copy_(self.theta["tr"])
         with self._agent_window():
-            if self.shard is None or self.shard.shard_tr:
+            if (self.shard is None or self.shard.shard_tr) and not live["tr"]:
                 self.msg["tr"].copy_(self.theta["tr"])
-            self.msg["critic"].copy_(self.theta["critic"])
+            if not live["critic"]:
+                self.msg["critic"].copy_(self.theta["critic"])
+        if self._td_from_fit_forward(B):
+            # first epoch of a block, nothing cached yet: the critic's fit would open with a forward pass of the live critic (its
+            # message still equals the live net) over the s rows.  Run that pass NOW: the TD target then takes V(ns) from those
+            # activations shifted by one row, as it does in every later epoch, instead of a forward pass of its own over the ns
+            # rows plus a W1 split -- the same products summed in the same order -- and the fit finds its step-0 activations cached.
+            self._layer1("s", self.theta["critic"], "critic", B, buf=self.a1net["critic"])
+            self.a1_cached["critic"] = True
         # TD target first (it depends on the live critic only), so the adversaries' message generators --
         # one latency-bound workgroup per (seed, adversary) -- can run on a side stream UNDER the cooperative
         # agents' local fits: they touch disjoint parameter rows and meet again at the consensus step
@@ -1515,6 +1576,8 @@ class RPBCACEngine:
         key = (B, self.lat_active, bool(self.td_shortcut), bool(self.rows_episode_aligned), bool(self.k1_circulant), bool(self.cfg.regular),
                bool(self.reuse_activations), self.cap, self.lib.rcmarl_lattice_f16_mode(), os.environ.get("RCMARL_LAT_W8"),
                os.environ.get("RCMARL_MIDFIT"),
+               # which fits start from the live net (their step 0 has theta's pointers, and the epoch has no copy in front)
+               self._fit_from_live("tr", "sa", B, self.coop), self._fit_from_live("critic", "s", B, self.coop),
                # the adversaries' launch form is re-read every epoch (AdversaryPath._multi_ok, phase1): a captured epoch belongs to one form
                bool(hasattr(self, "adv") and self.adv._multi_ok()), os.environ.get("RCMARL_ADV_ASYNC", "1"))
         g = self._graphs.get(key)

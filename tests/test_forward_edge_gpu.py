@@ -1,0 +1,22 @@
+"""Layer-1 lattice forward, last row tile: wavefronts without a live replay row skip the matrix work -- on a real MI355X through the
+product library, both wavefront forms and both operand forms."""
+import pytest
+
+import forward_edge_checks as FC
+from test_kernels_gpu import GpuBackend
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def bk():
+    return GpuBackend()
+
+
+@pytest.mark.parametrize("w8", ["0", "1"])
+@pytest.mark.parametrize("mode", [3, 0])
+@pytest.mark.parametrize("B", FC.EDGES)
+def test_rows_below_B_equal_the_full_tile_and_rows_beyond_keep_their_sentinel(bk, B, mode, w8, monkeypatch, lattice_form):
+    lattice_form(bk, mode)
+    monkeypatch.setenv("RCMARL_LAT_W8", w8)
+    FC.check_forward_edge(bk, B)
