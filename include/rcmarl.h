@@ -82,6 +82,23 @@ int rcmarl_consensus_params_ragged(const float* msg, float* theta, const int* nb
                                    const rcmarl_ragged_class* classes, int n_classes, int S, int N, int ldp, int P_hid,
                                    float* lo_dbg, float* hi_dbg, void* stream);
 
+/* Clip report: what K1's clip window trims, per in-neighbour slot.  For every cooperative agent i and slot k < d_i:
+ *   below[s][i][k] += #{p < P_hid : msg[s][nbr[i][k]][p] < lower(s, i, p)},   above: the same with > upper,
+ * lower / upper being the window with the bits K1 produces for that (d, H): the generated selection network where the K1 entry of
+ * the same name uses one (the ragged entry: d <= 20), rank counting otherwise.  Comparisons are IEEE strict: a NaN is never
+ * counted, nor -0 against +0.  below / above are int64 [S][N][ldc], ldc >= max d, and are ADDED to; slots k >= d_i, rows of agents
+ * that are not cooperative (not in order[]) and columns >= P_hid are never touched.  H == 0 (every class): RCMARL_OK without a
+ * launch.  scratch: rcmarl_consensus_clip_counts_scratch(S, N, ldc, P_hid) ints of device memory owned by the caller (per-launch
+ * 32-bit partials; no contents carried between calls).  Nothing is allocated and nothing read back: the same integers on every
+ * run, safe inside a captured graph.  RCMARL_ERR_ARG before any HIP call for: a null pointer, ldp % 64, d < 2H+1, d > N, ldc < d,
+ * P_hid > ldp, null scratch when the query is non-zero.  RCMARL_ERR_UNSUPPORTED where rcmarl_consensus_params is. */
+int rcmarl_consensus_clip_counts(const float* msg, const int* nbr, const int* coop, long long* below, long long* above,
+                                 int* scratch, int S, int N, int ldp, int P_hid, int d, int H, int ldc, void* stream);
+int rcmarl_consensus_clip_counts_ragged(const float* msg, const int* nbr_off, const int* nbr_idx, const int* order,
+                                        const rcmarl_ragged_class* classes, int n_classes, long long* below, long long* above,
+                                        int* scratch, int S, int N, int ldp, int P_hid, int ldc, void* stream);
+int rcmarl_consensus_clip_counts_scratch(int S, int N, int ldc, int P_hid);   /* ints of caller-owned scratch; 0 if none is needed */
+
 /* K4 layer 1 forward (shared input => one GEMM per seed), Keras Dense + LeakyReLU(0.1):
  * a1t[s][n*hid+j][b] = lrelu(sum_k x[s][b][k]*W1[s][n][k][j] + b1[s][n][j]).
  * Replaces the first Dense of every model call at agents/resilient_CAC_agents.py:66,79,95-97,114,181,201. */

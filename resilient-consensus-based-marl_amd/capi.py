@@ -62,6 +62,14 @@ SIGNATURES = {
     # msg, theta, nbr_off, nbr_idx, order, classes (host array of RaggedClass), n_classes, S, N, ldp, P_hid, lo_dbg, hi_dbg, stream
     "rcmarl_consensus_params_ragged": [c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p, c_int, c_int, c_int, c_int, c_int,
                                        c_f32p, c_f32p, c_stream],
+    # clip report (csrc/consensus_params.hip): msg, nbr, coop, below, above, scratch, S, N, ldp, P_hid, d, H, ldc, stream
+    "rcmarl_consensus_clip_counts": [c_f32p, c_i32p, c_i32p, C.c_void_p, C.c_void_p, c_i32p, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_int, c_stream],
+    # msg, nbr_off, nbr_idx, order, classes (host array of RaggedClass), n_classes, below, above, scratch, S, N, ldp, P_hid, ldc, stream
+    "rcmarl_consensus_clip_counts_ragged": [c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_i32p,
+                                            c_int, c_int, c_int, c_int, c_int, c_stream],
+    # S, N, ldc, P_hid -> ints of scratch
+    "rcmarl_consensus_clip_counts_scratch": [c_int, c_int, c_int, c_int],
     # a1t, theta, msg, nbr_off, nbr_idx, order, classes (host), n_classes, partials, agg_out, S, N, B, in_dim, hid, ldp, ldb, stream
     "rcmarl_consensus_head_ragged": [c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p, c_int, c_f32p, c_f32p, c_int,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_stream],
@@ -265,7 +273,7 @@ SIGNATURES = {
 }
 UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_layout", "rcmarl_lattice_forget", "rcmarl_fit_partial_size", "rcmarl_lattice_set_f16_mode",  "rcmarl_actor_partial_size", "rcmarl_rows_per_chunk", "rcmarl_lattice_f16_mode",
              "rcmarl_wide_grad_size", "rcmarl_wide_rows_per_chunk", "rcmarl_wide_f16_mode", "rcmarl_wide_set_f16_mode",
-             "rcmarl_consensus_params_circulant_supported", "rcmarl_pk_supported", "rcmarl_pk_parts",
+             "rcmarl_consensus_params_circulant_supported", "rcmarl_consensus_clip_counts_scratch", "rcmarl_pk_supported", "rcmarl_pk_parts",
              "rcmarl_rollout_wide_supported", "rcmarl_minibatch_fit_wide_supported",
              "rcmarl_minibatch_fit_wide2_supported", "rcmarl_minibatch_actor_wide_supported"}
 

@@ -39,6 +39,16 @@ __device__ __forceinline__ float rc_div_fast(float x) {
   return fmaf(fmaf(-q0, (float)D, x), rcp, q0);
 }
 
+// The clip window of one (agent, column) from the generated network: [min(sorted(v)[H], v_0), max(sorted(v)[D-H-1], v_0)].
+// Shared by the aggregation below and by the clip-count kernel, so that both see the same bits.
+template <int D, int H>
+__device__ __forceinline__ void window_regs(const float (&v)[D], float& lower, float& upper) {
+  float lo, hi;
+  SelNet<D, H>::run(v, lo, hi);
+  lower = fminf(lo, v[0]);
+  upper = fmaxf(hi, v[0]);
+}
+
 // want_window: the caller stores lower/upper (debug outputs of the bit-exactness tests).  H == 0 (BASELINE configs[0],
 // agents/resilient_CAC_agents.py:50-56 with H = 0): the window is [min, max] of the d values, clipping is the identity and
 // the aggregate is the plain mean -- no selection network and no clamps unless the window itself is asked for.
@@ -47,19 +57,11 @@ __device__ __forceinline__ float aggregate_regs(const float (&v)[D], float& lowe
   float sum = 0.f;
   if (H == 0) {
     lower = upper = v[0];
-    if (want_window) {
-      float lo, hi;
-      SelNet<D, H>::run(v, lo, hi);
-      lower = fminf(lo, v[0]);
-      upper = fmaxf(hi, v[0]);
-    }
+    if (want_window) window_regs<D, H>(v, lower, upper);
 #pragma unroll
     for (int k = 0; k < D; ++k) sum += v[k];
   } else {
-    float lo, hi;
-    SelNet<D, H>::run(v, lo, hi);
-    lower = fminf(lo, v[0]);
-    upper = fmaxf(hi, v[0]);
+    window_regs<D, H>(v, lower, upper);
 #pragma unroll
     for (int k = 0; k < D; ++k) sum += __builtin_amdgcn_fmed3f(v[k], lower, upper);  // clamp
   }
@@ -422,8 +424,8 @@ size_t circ_smem(int N, int d, int G, int TC) { return 2 * ((size_t)(N + d + G -
 // Any (d, H) without a generated network: order statistics by rank counting
 // out of the LDS tile (O(d^2) LDS reads).  Correct for every d >= 2H+1; slow.
 // One agent, one column: nb = the agent's neighbour list, c = the lane's column of the [N][TC] tile.
-__device__ __forceinline__ float aggregate_rank_count(const float* tile, const int* nb, int log2tc, int c, int d, int H,
-                                                      float& lower, float& upper) {
+__device__ __forceinline__ void window_rank_count(const float* tile, const int* nb, int log2tc, int c, int d, int H,
+                                                  float& lower, float& upper) {
   const float own = tile[(nb[0] << log2tc) + c];
   float lo = own, hi = own;
   for (int k = 0; k < d; ++k) {
@@ -438,6 +440,11 @@ __device__ __forceinline__ float aggregate_rank_count(const float* tile, const i
   }
   lower = fminf(lo, own);
   upper = fmaxf(hi, own);
+}
+
+__device__ __forceinline__ float aggregate_rank_count(const float* tile, const int* nb, int log2tc, int c, int d, int H,
+                                                      float& lower, float& upper) {
+  window_rank_count(tile, nb, log2tc, c, d, H, lower, upper);
   float sum = 0.f;
   for (int k = 0; k < d; ++k) sum += __builtin_amdgcn_fmed3f(tile[(nb[k] << log2tc) + c], lower, upper);
   return sum / (float)d;
@@ -606,6 +613,273 @@ bool launch_v2(const float* msg, float* theta, const int* nbr, const int* coop, 
   }
 }
 
+// ---- clip report: what the clip window trims, per in-neighbour slot ---------------------------------------------------------
+// For every cooperative agent i and slot k of its in-neighbourhood: how many of the P_hid hidden-layer parameters of neighbour k's
+// message lie strictly below / above i's clip window (the window K1 computes and then discards: window_regs / window_rank_count).
+//
+// Grid = (column ranges, agent groups, seeds).  A workgroup walks the column tiles of its range; per tile it stages the [N][TC]
+// image K1 stages, but ONLY the rows its agent group reads (a byte map in LDS, filled once from the group's neighbour lists: a group
+// of G consecutive agents of a circulant graph fetches G + d - 1 rows, not N).  A wavefront owns TC-column slices of whole agents;
+// a slot's comparison becomes popcount(ballot) and one lane adds it to the group's counters in LDS (one wavefront per agent: no
+// two wavefronts share a counter).  After the last tile the counters go to `scratch` with plain stores -- every (range, seed,
+// agent, slot) entry has exactly one writer -- and k_clip_fold adds the ranges' partials into the 64-bit accumulators, one thread
+// per accumulator.  No atomics on global memory: the same integers on every run.
+struct ClipGraph {
+  const int* nbr; const int* coop; int d;                               // regular graph: nbr[N][d], coop[N]
+  const int* nbr_off; const int* nbr_idx; const int* order;             // irregular graph (CSR; order[] lists the cooperative agents)
+  __device__ __forceinline__ const int* nb(int i) const { return nbr ? nbr + (size_t)i * d : nbr_idx + nbr_off[i]; }
+};
+
+struct ClipPlan {
+  bool ok;
+  int log2tc, tiles_per_seed, CR, tiles_per_range, GA, AG;
+  size_t smem;
+  long long scratch_ints;
+};
+
+// Everything the launch shape depends on is (S, N, ldc, P_hid): the scratch query and the entry points agree by construction.
+ClipPlan clip_plan(int S, int N, int ldc, int P_hid) {
+  ClipPlan p{};
+  if (S <= 0 || N <= 0 || ldc <= 0 || P_hid <= 0) return p;
+  p.log2tc = 6;                                             // widest column tile whose [N][TC] image fits 64 KiB, as K1
+  while (p.log2tc > 2 && ((size_t)N << p.log2tc) * sizeof(float) > 64 * 1024) --p.log2tc;
+  if (((size_t)N << p.log2tc) * sizeof(float) > 64 * 1024) return p;
+  p.tiles_per_seed = rc_ceil_div(P_hid, 1 << p.log2tc);
+  // agents per group: both counters of a group within 12 KiB, so that image + counters + row map leave two workgroups per CU
+  int ga = 12288 / (8 * ldc);
+  ga = ga < 1 ? 1 : (ga > N ? N : ga);
+  p.AG = rc_ceil_div(N, ga);
+  p.GA = rc_ceil_div(N, p.AG);
+  p.AG = rc_ceil_div(N, p.GA);
+  // column ranges: enough workgroups for the chip, at most 16 partial planes, no empty range
+  const long long per_range = (long long)p.AG * S;
+  const int target = rc_persistent_grid(1024);
+  long long cr = (target + per_range - 1) / per_range;
+  if (cr > 16) cr = 16;
+  if (cr > p.tiles_per_seed) cr = p.tiles_per_seed;
+  if (cr < 1) cr = 1;
+  const long long plane = 2LL * S * N * ldc;                // below + above of one column range
+  while (cr > 1 && cr * plane > 0x7fffffffLL) --cr;
+  if (cr * plane > 0x7fffffffLL) return p;
+  p.tiles_per_range = rc_ceil_div(p.tiles_per_seed, (int)cr);
+  p.CR = rc_ceil_div(p.tiles_per_seed, p.tiles_per_range);
+  p.scratch_ints = p.CR * plane;
+  p.smem = ((size_t)N << p.log2tc) * sizeof(float) + 2 * (size_t)p.GA * ldc * sizeof(int) + (((size_t)N + 15) & ~(size_t)15);
+  p.ok = p.AG <= 65535 && S <= 65535;
+  return p;
+}
+
+struct ClipCtx {
+  const float* tile; int* cnt;                              // counters: below [GA][ldc], then above [GA][ldc]
+  int log2tc, c, g0, ga, GA, ldc, rpp;                      // rpp: agents the workgroup takes per pass
+  bool col_ok;
+  unsigned long long submask;                               // the lanes that hold this lane's agent
+};
+
+// One agent (per TC lanes): window, then one ballot pair per slot.  nb must be readable for d entries for every lane; `valid`
+// lanes own a real agent whose counters are cb / ca.  Every lane of the wavefront runs this (ballots).
+template <int D, int H>
+__device__ __forceinline__ void clip_agent(const ClipCtx& x, const int* nb, bool valid, int* cb, int* ca, int d, int Hrt) {
+  const bool ok = valid && x.col_ok;
+  const int tcm = (1 << x.log2tc) - 1;
+  float lower, upper;
+  if constexpr (D > 0) {
+    float v[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) v[k] = x.tile[(nb[k] << x.log2tc) + x.c];
+    window_regs<D, H>(v, lower, upper);
+    if (x.log2tc == 6) {
+      // one wavefront = one agent (`valid` is uniform): the counts are scalars; lane k keeps slot k in a register and the
+      // counters in LDS take one add per lane and tile (slots from 64 on go there directly)
+      int accb = 0, acca = 0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const int nbl = (int)__builtin_popcountll(rc_ballot(ok && v[k] < lower));
+        const int nab = (int)__builtin_popcountll(rc_ballot(ok && v[k] > upper));
+        if (k < 64) {
+          accb += x.c == k ? nbl : 0;
+          acca += x.c == k ? nab : 0;
+        } else if (valid && x.c == k - 64) {
+          atomicAdd(cb + k, nbl);
+          atomicAdd(ca + k, nab);
+        }
+      }
+      if (valid && x.c < (D < 64 ? D : 64)) {
+        atomicAdd(cb + x.c, accb);
+        atomicAdd(ca + x.c, acca);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const unsigned long long mb = rc_ballot(ok && v[k] < lower), ma = rc_ballot(ok && v[k] > upper);
+        if (valid && x.c == (k & tcm)) {
+          atomicAdd(cb + k, (int)__builtin_popcountll(mb & x.submask));
+          atomicAdd(ca + k, (int)__builtin_popcountll(ma & x.submask));
+        }
+      }
+    }
+  } else {
+    window_rank_count(x.tile, nb, x.log2tc, x.c, d, Hrt, lower, upper);
+    for (int k = 0; k < d; ++k) {
+      const float v = x.tile[(nb[k] << x.log2tc) + x.c];
+      const unsigned long long mb = rc_ballot(ok && v < lower), ma = rc_ballot(ok && v > upper);
+      if (valid && x.c == (k & tcm)) {
+        atomicAdd(cb + k, (int)__builtin_popcountll(mb & x.submask));
+        atomicAdd(ca + k, (int)__builtin_popcountll(ma & x.submask));
+      }
+    }
+  }
+}
+
+// The agents of one class that belong to this workgroup's group [g0, g0 + ga).  Regular graph (no order[]): agent = position.
+__device__ __forceinline__ int clip_agent_of(const ClipGraph& g, int first, int j, int j_end, int g0, int ga) {
+  if (j >= j_end) return -1;
+  const int i = g.order ? g.order[first + j] : j;
+  if (i < g0 || i >= g0 + ga) return -1;
+  if (g.coop && !g.coop[i]) return -1;
+  return i;
+}
+
+template <int D, int H>
+__device__ __forceinline__ void clip_class(const ClipCtx& x, const ClipGraph& g, int first, int count, int d, int Hrt) {
+  const int j_begin = g.order ? 0 : x.g0, j_end = g.order ? count : x.g0 + x.ga;
+  const int rpp = x.rpp;
+  const int fallback = g.order ? g.order[first] : x.g0;     // an agent of this class: its list has d entries
+  for (int j0 = j_begin; j0 < j_end; j0 += rpp) {
+    int i = clip_agent_of(g, first, j0 + (int)(threadIdx.x >> x.log2tc), j_end, x.g0, x.ga);
+    if (x.log2tc == 6) {                                    // one wavefront = one agent: an SGPR index, a uniform skip
+      i = __builtin_amdgcn_readfirstlane(i);
+      if (i < 0) continue;
+    }
+    const bool valid = i >= 0;
+    const int a = valid ? i - x.g0 : 0;
+    clip_agent<D, H>(x, g.nb(valid ? i : fallback), valid, x.cnt + a * x.ldc, x.cnt + (x.GA + a) * x.ldc, d, Hrt);
+  }
+}
+
+// WD > 0: the regular entry's kernel for one generated network (WD, WH); WD == 0: any classes -- networks up to
+// RC_RAGGED_MAX_NET_D through a scalar switch, rank counting otherwise (the rule of k_consensus_params_ragged).
+// Workgroup size: the image and the counters leave two workgroups per CU at most, so the wavefronts that hide the LDS latency have
+// to come from the workgroup itself: 1024 threads (128 VGPRs each) wherever the network fits them, 512 for the widest networks.
+template <int WD> constexpr int clip_threads() { return WD <= 34 ? 1024 : 512; }
+
+template <int WD, int WH>
+__global__ __launch_bounds__(clip_threads<WD>()) void k_clip_counts(const float* __restrict__ msg, const ClipGraph g,
+                                                                    const RaggedClasses cls, int* __restrict__ scratch, int N,
+                                                                    int ldp, int P_hid, int log2tc, int ldc, int tiles_per_seed,
+                                                                    int tiles_per_range, int GA) {
+  RCMARL_DYN_SMEM(float, tile);
+  const int TC = 1 << log2tc, lq = log2tc - 2, nt = clip_threads<WD>();
+  int* cnt = reinterpret_cast<int*>(tile + ((size_t)N << log2tc));
+  unsigned char* need = reinterpret_cast<unsigned char*>(cnt + 2 * GA * ldc);
+  const int r = blockIdx.x, g0 = blockIdx.y * GA, s = blockIdx.z, S = gridDim.z, CR = gridDim.x;
+  const int ga = min(GA, N - g0);
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < 2 * GA * ldc; idx += nt) cnt[idx] = 0;
+  for (int idx = tid; idx < N; idx += nt) need[idx] = 0;
+  __syncthreads();
+  // the rows this group reads
+  for (int q = 0; q < cls.n; ++q) {
+    const int d = cls.d[q], first = cls.first[q], count = cls.count[q];
+    if (cls.H[q] == 0) continue;
+    const int j_begin = g.order ? 0 : g0, j_end = g.order ? count : g0 + ga;
+    for (int idx = tid; idx < (j_end - j_begin) * d; idx += nt) {
+      const int jj = idx / d, k = idx - jj * d;
+      const int i = clip_agent_of(g, first, j_begin + jj, j_end, g0, ga);
+      if (i >= 0) need[g.nb(i)[k]] = 1;
+    }
+  }
+  ClipCtx x;
+  x.tile = tile; x.cnt = cnt; x.log2tc = log2tc; x.c = tid & (TC - 1); x.rpp = nt >> log2tc; x.g0 = g0; x.ga = ga; x.GA = GA; x.ldc = ldc;
+  x.submask = TC == 64 ? ~0ull : (((1ull << TC) - 1ull) << (((tid & 63) >> log2tc) << log2tc));
+  const int t_begin = r * tiles_per_range, t_end = min(tiles_per_seed, t_begin + tiles_per_range);
+  const float* ms = msg + (size_t)s * N * ldp;
+  for (int t = t_begin; t < t_end; ++t) {
+    const int c0 = t << log2tc;
+    __syncthreads();                                        // the row map is complete / every wave is done with the previous image
+    for (int idx = tid; idx < (N << lq); idx += nt) {
+      const int row = idx >> lq, c4 = 4 * (idx & ((1 << lq) - 1));
+      if (need[row])
+        *reinterpret_cast<float4*>(tile + ((size_t)row << log2tc) + c4) =
+            *reinterpret_cast<const float4*>(ms + (size_t)row * ldp + c0 + c4);
+    }
+    __syncthreads();
+    x.col_ok = (c0 + x.c) < P_hid;
+    for (int q = 0; q < cls.n; ++q) {
+      const int d = cls.d[q], H = cls.H[q], first = cls.first[q], count = cls.count[q];
+      if (H == 0) continue;                                 // window = [min, max]: nothing is clipped
+      if constexpr (WD > 0) {
+        clip_class<WD, WH>(x, g, first, count, d, H);
+      } else {
+        switch (d <= RC_RAGGED_MAX_NET_D ? d * 64 + H : -1) {
+#define RC_CCASE(DD, HH)                                                                                                     \
+          case (DD <= RC_RAGGED_MAX_NET_D ? DD * 64 + HH : -2 - (DD * 64 + HH)):                                             \
+            if constexpr (DD <= RC_RAGGED_MAX_NET_D && HH > 0) clip_class<DD, HH>(x, g, first, count, d, H);                 \
+            break;
+          RCMARL_SELNET_COMBOS(RC_CCASE)
+#undef RC_CCASE
+          default:
+            clip_class<0, 0>(x, g, first, count, d, H);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // partials of this (range, seed): plain stores, one writer per entry
+  const size_t plane = (size_t)CR * S * N * ldc;
+  int* part = scratch + ((size_t)r * S + s) * N * ldc;
+  for (int q = 0; q < cls.n; ++q) {
+    const int d = cls.d[q], first = cls.first[q], count = cls.count[q];
+    if (cls.H[q] == 0) continue;
+    const int j_begin = g.order ? 0 : g0, j_end = g.order ? count : g0 + ga;
+    for (int idx = tid; idx < (j_end - j_begin) * d; idx += nt) {
+      const int jj = idx / d, k = idx - jj * d;
+      const int i = clip_agent_of(g, first, j_begin + jj, j_end, g0, ga);
+      if (i >= 0) {
+        part[(size_t)i * ldc + k] = cnt[(i - g0) * ldc + k];
+        part[plane + (size_t)i * ldc + k] = cnt[(GA + i - g0) * ldc + k];
+      }
+    }
+  }
+}
+
+// below/above[s][i][k] += sum over the column ranges' partials: one thread per accumulator (its only writer)
+__global__ __launch_bounds__(256) void k_clip_fold(const int* __restrict__ scratch, const ClipGraph g, const RaggedClasses cls,
+                                                   long long* __restrict__ below, long long* __restrict__ above, int N, int ldc,
+                                                   int CR) {
+  const int s = blockIdx.y, S = gridDim.y;
+  const size_t plane = (size_t)CR * S * N * ldc, range = (size_t)S * N * ldc;
+  for (int q = 0; q < cls.n; ++q) {
+    const int d = cls.d[q], first = cls.first[q];
+    if (cls.H[q] == 0) continue;
+    const int j_end = g.order ? cls.count[q] : N;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < j_end * d; idx += gridDim.x * 256) {
+      const int jj = idx / d, k = idx - jj * d;
+      const int i = clip_agent_of(g, first, jj, j_end, 0, N);
+      if (i < 0) continue;
+      const size_t o = ((size_t)s * N + i) * ldc + k;
+      long long nb_ = 0, na_ = 0;
+      for (int r = 0; r < CR; ++r) { nb_ += scratch[r * range + o]; na_ += scratch[plane + r * range + o]; }
+      below[o] += nb_;
+      above[o] += na_;
+    }
+  }
+}
+
+template <int WD, int WH>
+int clip_launch(const ClipPlan& p, const float* msg, const ClipGraph& g, const RaggedClasses& cls, long long* below,
+                long long* above, int* scratch, int S, int N, int ldp, int P_hid, int ldc, void* stream) {
+  if (!k1_want_lds(k_clip_counts<WD, WH>, p.smem)) return RCMARL_ERR_LAUNCH;
+  RCMARL_LAUNCH((k_clip_counts<WD, WH>), dim3(p.CR, p.AG, S), dim3(clip_threads<WD>()), p.smem, stream, msg, g, cls, scratch, N, ldp, P_hid,
+                p.log2tc, ldc, p.tiles_per_seed, p.tiles_per_range, p.GA);
+  int rc = rcmarl_check_launch();
+  if (rc != RCMARL_OK) return rc;
+  int fb = rc_ceil_div(N * ldc, 256);
+  if (fb > 64) fb = 64;
+  RCMARL_LAUNCH(k_clip_fold, dim3(fb, S), dim3(256), 0, stream, (const int*)scratch, g, cls, below, above, N, ldc, p.CR);
+  return rcmarl_check_launch();
+}
+
 }  // namespace
 
 // C-ABI: see include/rcmarl.h
@@ -762,6 +1036,72 @@ RCMARL_EXPORT int rcmarl_consensus_params_ragged(const float* msg, float* theta,
     RCMARL_LAUNCH(k_consensus_params_ragged, dim3(nwg), dim3(256), smem, stream, msg, theta, nbr_off, nbr_idx, order, cls, N, ldp,
                   P_hid, log2tc, tiles_per_seed, total_tiles, lo_dbg, hi_dbg);
     const int rc = rcmarl_check_launch();
+    if (rc != RCMARL_OK) return rc;
+  }
+  return RCMARL_OK;
+}
+
+// ---- clip report (k_clip_counts above; include/rcmarl.h has the contract) ----------------------------------------------------
+RCMARL_EXPORT int rcmarl_consensus_clip_counts_scratch(int S, int N, int ldc, int P_hid) {
+  const ClipPlan p = clip_plan(S, N, ldc, P_hid);
+  return p.ok ? (int)p.scratch_ints : 0;
+}
+
+RCMARL_EXPORT int rcmarl_consensus_clip_counts(const float* msg, const int* nbr, const int* coop, long long* below,
+                                               long long* above, int* scratch, int S, int N, int ldp, int P_hid, int d, int H,
+                                               int ldc, void* stream) {
+  if (!msg || !nbr || !coop || !below || !above || S <= 0 || N <= 0 || d <= 0 || H < 0 || d < 2 * H + 1 || d > N || ldc < d ||
+      (ldp & 63) || P_hid <= 0 || P_hid > ldp)
+    return RCMARL_ERR_ARG;
+  const ClipPlan p = clip_plan(S, N, ldc, P_hid);
+  if (p.ok && p.scratch_ints > 0 && !scratch) return RCMARL_ERR_ARG;
+  if (H == 0) return RCMARL_OK;                            // the window is [min, max]: nothing can be clipped
+  if (!p.ok) return RCMARL_ERR_UNSUPPORTED;
+  ClipGraph g{nbr, coop, d, nullptr, nullptr, nullptr};
+  RaggedClasses cls{};
+  cls.n = 1; cls.d[0] = d; cls.H[0] = H; cls.first[0] = 0; cls.count[0] = N;
+  // a kernel of its own for the networks the switch of the general kernel leaves out (d > 20) and for the d = 2H+2 shapes of the
+  // reference's graphs; every other generated network runs through the switch, any other (d, H) counts ranks
+#define RC_CLIP_CASE(DD, HH)                                                                                          \
+  if constexpr (HH > 0 && (DD > RC_RAGGED_MAX_NET_D || DD == 2 * HH + 2)) {                                            \
+    if (d == DD && H == HH)                                                                                           \
+      return clip_launch<DD, HH>(p, msg, g, cls, below, above, scratch, S, N, ldp, P_hid, ldc, stream);               \
+  }
+  RCMARL_SELNET_COMBOS(RC_CLIP_CASE)
+#undef RC_CLIP_CASE
+  return clip_launch<0, 0>(p, msg, g, cls, below, above, scratch, S, N, ldp, P_hid, ldc, stream);
+}
+
+RCMARL_EXPORT int rcmarl_consensus_clip_counts_ragged(const float* msg, const int* nbr_off, const int* nbr_idx, const int* order,
+                                                      const rcmarl_ragged_class* classes, int n_classes, long long* below,
+                                                      long long* above, int* scratch, int S, int N, int ldp, int P_hid, int ldc,
+                                                      void* stream) {
+  if (!msg || !nbr_off || !nbr_idx || !order || !classes || !below || !above || n_classes <= 0 || S <= 0 || N <= 0 || ldc <= 0 ||
+      (ldp & 63) || P_hid <= 0 || P_hid > ldp)
+    return RCMARL_ERR_ARG;
+  bool any = false;
+  for (int q = 0; q < n_classes; ++q) {
+    const rcmarl_ragged_class& k = classes[q];
+    if (k.d <= 0 || k.d > N || k.H < 0 || k.d < 2 * k.H + 1 || k.first < 0 || k.count <= 0 || k.first > N - k.count || ldc < k.d)
+      return RCMARL_ERR_ARG;
+    any = any || k.H > 0;
+  }
+  const ClipPlan p = clip_plan(S, N, ldc, P_hid);
+  if (p.ok && p.scratch_ints > 0 && !scratch) return RCMARL_ERR_ARG;
+  if (!any) return RCMARL_OK;
+  if (!p.ok) return RCMARL_ERR_UNSUPPORTED;
+  ClipGraph g{nullptr, nullptr, 0, nbr_off, nbr_idx, order};
+  for (int q0 = 0; q0 < n_classes; q0 += RC_RAGGED_MAX_CLASSES) {      // (the fold of a chunk runs before the next chunk's counts)
+    RaggedClasses cls{};
+    cls.n = n_classes - q0 < RC_RAGGED_MAX_CLASSES ? n_classes - q0 : RC_RAGGED_MAX_CLASSES;
+    bool chunk_any = false;
+    for (int q = 0; q < cls.n; ++q) {
+      cls.d[q] = classes[q0 + q].d; cls.H[q] = classes[q0 + q].H;
+      cls.first[q] = classes[q0 + q].first; cls.count[q] = classes[q0 + q].count;
+      chunk_any = chunk_any || cls.H[q] > 0;
+    }
+    if (!chunk_any) continue;
+    const int rc = clip_launch<0, 0>(p, msg, g, cls, below, above, scratch, S, N, ldp, P_hid, ldc, stream);
     if (rc != RCMARL_OK) return rc;
   }
   return RCMARL_OK;

@@ -70,7 +70,7 @@ class EngineConfig:
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
                  local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID, adv_wide2="auto",
-                 w1_tiled="auto", fit_from_live="auto"):
+                 w1_tiled="auto", fit_from_live="auto", clip_report=False):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -105,6 +105,9 @@ class EngineConfig:
         if not any(fit_from_live is v for v in (True, False)) and fit_from_live != "auto":
             raise ValueError("fit_from_live must be 'auto', True or False")
         self.fit_from_live = fit_from_live
+        # clip report: count, per cooperative agent and in-neighbour slot, the hidden-layer parameters that fall below / above the
+        # clip window at every hidden-layer consensus step (RPBCACEngine.clip_report()); off: no launch, no buffer
+        self.clip_report = bool(clip_report)
         assert len(self.agent_label) == self.n_agents and len(self.in_nodes) == self.n_agents
         if np.ndim(H) == 0:
             self.H_per_agent = [int(H)] * self.n_agents
@@ -279,6 +282,18 @@ class RPBCACEngine:
         self.np_rngs = None                   # rng_mode='numpy': one RandomState-like object per seed
         self.shard = None                     # shard_agents(): ONE instance over several GPUs (wide critic)
         self._windowed = False
+        # clip report (EngineConfig.clip_report): int64 [S][N][dmax] accumulators per net and the count entry's scratch, allocated once
+        self.clip = None
+        if c.clip_report:
+            i64 = dict(dtype=torch.int64, device=self.dev)
+            dmax = c.d
+            self.clip = {"dmax": dmax, "steps": 0, "scratch": {}, "P_hid": {},
+                         "below": {k: torch.zeros(S, N, dmax, **i64) for k in ("critic", "tr")},
+                         "above": {k: torch.zeros(S, N, dmax, **i64) for k in ("critic", "tr")}}
+            for k in ("critic", "tr"):
+                g_hid = self.P[k] - (self.hid[k] + 1)
+                self.clip["P_hid"][k] = g_hid
+                self.clip["scratch"][k] = torch.zeros(max(1, lib.rcmarl_consensus_clip_counts_scratch(S, N, dmax, g_hid)), **i32)
 
     # ---- everything sized by the replay capacity ---------------------------------------------------
     def _alloc_row_buffers(self, cap):
@@ -596,6 +611,9 @@ class RPBCACEngine:
         force: shard even at world size 1, so that EVERY collective of the sharded instance runs through the communicator
         (the one-rank RCCL run on a single-GPU box: tests/test_rccl_one_rank_gpu.py, `bench.py --workload cfg5_shard`)."""
         from .parallel import ShardedConsensus, TorchComm, agent_range
+        if self.cfg.clip_report:
+            raise ValueError("agent sharding has no clip report: the column-sharded consensus (parallel.ShardedConsensus) never holds "
+                             "whole message rows (clip_report = True)")
         if not self.cfg.regular:
             raise ValueError("agent sharding needs a regular communication graph with one H: the column-sharded consensus "
                              "(parallel.ShardedConsensus) takes one (d, H)")
@@ -950,6 +968,10 @@ class RPBCACEngine:
             sd[k] = getattr(self, k).detach().cpu()
         if hasattr(self, "adv"):
             sd["adv"] = self.adv.state_dict()
+        if self.clip is not None:             # (only with EngineConfig.clip_report: files of other engines keep their keys)
+            sd["clip_report"] = {"steps": int(self.clip["steps"]),
+                                 "below": {k: v.detach().cpu() for k, v in self.clip["below"].items()},
+                                 "above": {k: v.detach().cpu() for k, v in self.clip["above"].items()}}
         sd["shape"] = {"H": self._ckpt_H(), "critic_hid": c.critic_hid, "actor_hid": c.actor_hid, "tr_hid": c.tr_hid, "buffer_size": c.buffer_size,
                        "n_ep_fixed": c.n_ep_fixed, "max_ep_len": c.max_ep_len, "nrow": c.nrow, "ncol": c.ncol, "rng_mode": c.rng_mode}
         if self.np_rngs is not None:          # plain tensors / numbers only, so the file loads with weights_only=True
@@ -992,6 +1014,15 @@ class RPBCACEngine:
         self.xs[self.cur].copy_(sd["xs"])
         for k in self._CKPT_TENSORS:
             getattr(self, k).copy_(sd[k])
+        if self.clip is not None:             # a file without the key (written with the switch off): the report starts from zero
+            cr = sd.get("clip_report")
+            for k in ("critic", "tr"):
+                for side in ("below", "above"):
+                    if cr is None:
+                        self.clip[side][k].zero_()
+                    else:
+                        self.clip[side][k].copy_(cr[side][k])
+            self.clip["steps"] = 0 if cr is None else int(cr["steps"])
         if "adv" in sd:
             self._require_adversary_support()
             self.adv.load_state_dict(sd["adv"])
@@ -1308,6 +1339,8 @@ class RPBCACEngine:
             sc.consensus()
             sc.gather(self.theta[net])
             return
+        if self.clip is not None:
+            self._clip_counts(net, g_hid)
         if not c.regular:
             if self.classes:
                 L.rcmarl_consensus_params_ragged(self.msg[net].data_ptr(), self.theta[net].data_ptr(), self.nbr_off.data_ptr(),
@@ -1320,6 +1353,55 @@ class RPBCACEngine:
             L.rcmarl_consensus_params(self.msg[net].data_ptr(), self.theta[net].data_ptr(), self.nbr.data_ptr(),
                                       self.coop.data_ptr(), self.S, self.N, self.ldp[net], g_hid, c.d, c.H, None, None,
                                       self.stream)
+
+    def _clip_counts(self, net, g_hid):
+        """clip report: count what the window of the K1 call that follows trims from self.msg[net], per in-neighbour slot"""
+        L, c, cl = self.lib, self.cfg, self.clip
+        assert g_hid == cl["P_hid"][net]
+        below, above, scratch = cl["below"][net].data_ptr(), cl["above"][net].data_ptr(), cl["scratch"][net].data_ptr()
+        if not c.regular:
+            if self.classes:
+                L.rcmarl_consensus_clip_counts_ragged(self.msg[net].data_ptr(), self.nbr_off.data_ptr(), self.nbr_idx.data_ptr(),
+                                                      self.order.data_ptr(), self.class_table, len(self.classes), below, above, scratch,
+                                                      self.S, self.N, self.ldp[net], g_hid, cl["dmax"], self.stream)
+        else:
+            L.rcmarl_consensus_clip_counts(self.msg[net].data_ptr(), self.nbr.data_ptr(), self.coop.data_ptr(), below, above, scratch,
+                                           self.S, self.N, self.ldp[net], g_hid, c.d, c.H, cl["dmax"], self.stream)
+
+    def clip_report(self, reset=False):
+        """What the resilient aggregation trimmed since the start (or the last reset): {net: {...}} for net in ("critic", "tr") with
+        below, above: int64 [S][N][dmax] -- for recipient i and slot k of in_nodes[i], the hidden-layer parameters of that
+            neighbour's message that fell strictly below / above i's clip window, summed over the consensus steps
+            (rows of non-cooperative agents and slots k >= d_i stay 0);
+        steps: hidden-layer consensus steps accumulated; P_hid: hidden-layer parameters per message; in_nodes: the graph;
+        sender_rate: float64 [S][N] -- the fraction of sender j's values that its cooperative listeners (slots k >= 1) clipped,
+            NaN where nobody listens to j."""
+        if self.clip is None:
+            raise ValueError("the clip report is off: build the engine with EngineConfig(clip_report=True)")
+        c, cl = self.cfg, self.clip
+        self.sync()
+        out = {}
+        for net in ("critic", "tr"):
+            below, above = cl["below"][net].cpu().numpy().copy(), cl["above"][net].cpu().numpy().copy()
+            clipped = np.zeros((self.S, self.N), np.float64)
+            listeners = np.zeros(self.N, np.int64)
+            for i, row in enumerate(c.in_nodes):
+                if not self.coop_np[i]:
+                    continue
+                for k in range(1, len(row)):
+                    clipped[:, row[k]] += below[:, i, k] + above[:, i, k]
+                    listeners[row[k]] += 1
+            denom = float(cl["steps"]) * cl["P_hid"][net] * listeners.astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rate = np.where(denom > 0, clipped / np.where(denom > 0, denom, 1.0), np.nan)
+            out[net] = {"below": below, "above": above, "steps": int(cl["steps"]), "P_hid": int(cl["P_hid"][net]),
+                        "in_nodes": [list(r) for r in c.in_nodes], "sender_rate": rate}
+        if reset:
+            for net in ("critic", "tr"):
+                cl["below"][net].zero_()
+                cl["above"][net].zero_()
+            cl["steps"] = 0
+        return out
 
     def _cached_rows_ok(self, net, row0, nrows, cached=None):
         """May values of `net` on replay rows row0..row0+nrows come from the activations the consensus step left in
@@ -1571,6 +1653,8 @@ class RPBCACEngine:
         return not getattr(self.lib, "enabled", False)            # bench.py's per-kernel timing wrapper records events per launch
 
     def _epoch(self, B, epoch, t0):
+        if self.clip is not None:
+            self.clip["steps"] += 1               # one hidden-layer consensus step per net and epoch, replayed epochs included
         if epoch == 0 or not self._graph_wanted() or not (self.a1_cached["critic"] and self.a1_cached["tr"]):
             return self._epoch_body(B, t0)
         key = (B, self.lat_active, bool(self.td_shortcut), bool(self.rows_episode_aligned), bool(self.k1_circulant), bool(self.cfg.regular),

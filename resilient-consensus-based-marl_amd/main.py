@@ -56,6 +56,8 @@ def build_parser():
     parser.add_argument('--ncol', type=int, default=5)
     parser.add_argument('--rng_mode', choices=['numpy', 'device'], default='numpy')
     parser.add_argument('--verbose', action='store_true')
+    parser.add_argument('--clip_report', action='store_true',
+                        help='count what the resilient aggregation trims, per recipient and in-neighbour; written to clip_report.npz')
     return parser
 
 
@@ -108,6 +110,23 @@ def save_weights(path, agent_weights):
     np.save(path, obj, allow_pickle=True)
 
 
+def save_clip_report(path, report):
+    """RPBCACEngine.clip_report() of one seed as plain arrays: <net>_below, <net>_above (int64 [N][dmax]), <net>_sender_rate
+    (float64 [N]), <net>_steps, <net>_P_hid, and in_nodes padded with -1 to [N][dmax]."""
+    out = {}
+    for net, r in report.items():
+        for k in ("below", "above", "sender_rate"):
+            out["%s_%s" % (net, k)] = np.asarray(r[k])
+        out[net + "_steps"] = np.int64(r["steps"])
+        out[net + "_P_hid"] = np.int64(r["P_hid"])
+        rows = r["in_nodes"]
+        pad = np.full((len(rows), max(len(row) for row in rows)), -1, np.int64)
+        for i, row in enumerate(rows):
+            pad[i, :len(row)] = row
+        out["in_nodes"] = pad
+    np.savez(path, **out)
+
+
 def main(argv=None, engine_hook=None):
     """engine_hook: (lib, device) handed to train_RPBCAC -- tests inject the hipemu build; None = the product library on cuda."""
     args = vars(build_parser().parse_args(argv))
@@ -126,6 +145,8 @@ def main(argv=None, engine_hook=None):
                      initial_state=s_initial, randomize_state=True, scaling=True)
     agent_weights, sim_data = training.train_RPBCAC(env, agents, args, engine_hook=engine_hook)
     sim_data.to_pickle("sim_data.pkl")
+    if args['clip_report']:
+        save_clip_report("clip_report.npz", sim_data.attrs['clip_report'])
     save_weights('pretrained_weights.npy', agent_weights)
     np.save('desired_state.npy', s_desired, allow_pickle=True)
     return agent_weights, sim_data

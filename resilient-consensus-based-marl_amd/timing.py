@@ -35,6 +35,11 @@ WORK = {
     "rcmarl_consensus_params": lambda a: (0.0, 8.0 * a[4] * a[5] * a[7]),
     # msg, theta, coop, S, N, ldp, P_hid, ...
     "rcmarl_consensus_params_circulant": lambda a: (0.0, 8.0 * a[3] * a[4] * a[6]),
+    # clip report -- msg, nbr, coop, below, above, scratch, S, N, ldp, P_hid, ...: the message matrix read once (the compulsory
+    # traffic; the kernel re-reads rows shared between agent groups), counters negligible
+    "rcmarl_consensus_clip_counts": lambda a: (0.0, 4.0 * a[6] * a[7] * a[9]),
+    # msg, nbr_off, nbr_idx, order, classes, n_classes, below, above, scratch, S, N, ldp, P_hid, ...
+    "rcmarl_consensus_clip_counts_ragged": lambda a: (0.0, 4.0 * a[9] * a[10] * a[12]),
     # a1t, theta, y, partials, S, N, B, in_dim, hid: layers 2-3 fwd+bwd ~ (8 h^2 + 12 h) flops per (row, agent)
     "rcmarl_mid_fit": lambda a: (a[4] * a[5] * a[6] * (8.0 * a[8] ** 2 + 12.0 * a[8]), 8.0 * a[4] * a[5] * a[6] * a[8]),
     # lattice path: fp32-EQUIVALENT flops 2*M*N*K (the kernel executes 2x that on the f16 matrix core, 3x in the bf16 form)

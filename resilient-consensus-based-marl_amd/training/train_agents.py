@@ -12,6 +12,8 @@ Extra (optional) ``args`` keys on top of the reference's (main.py:26-44):
              stream exactly as the reference does (agents:208-219, grid_world:40);
              'device': counter-based Philox stream on the GPU (no host round trip)
   verbose    print one line per episode like the reference (:174)
+  clip_report  any truthy value: count what the resilient aggregation trims (EngineConfig.clip_report); the returned DataFrame
+             then carries ``attrs['clip_report']`` = {net: {below, above, steps, P_hid, in_nodes, sender_rate}} of the run
 """
 import numpy as np
 import pandas as pd
@@ -49,7 +51,7 @@ def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
                        buffer_size=args['buffer_size'], common_reward=_truthy(args['common_reward']), nrow=env.nrow,
                        ncol=env.ncol, n_seeds=1, rng_mode=args.get('rng_mode', 'numpy'),
                        scaling=bool(getattr(env, 'scaling', not np.isscalar(env.mean_state))),
-                       randomize_state=env.randomize_state)
+                       randomize_state=env.randomize_state, clip_report=_truthy(args.get('clip_report')))
     lib, device = engine_hook if engine_hook is not None else (None, "cuda")
     eng = RPBCACEngine(cfg, seeds=[int(args.get('random_seed', 0))], device=device, lib=lib)
     # ---- agents -> stacked parameter matrices
@@ -84,6 +86,10 @@ def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
     sim_data = pd.DataFrame({"True_team_returns": logs["True_team_returns"][:, 0],
                              "True_adv_returns": logs["True_adv_returns"][:, 0],
                              "Estimated_team_returns": logs["Estimated_team_returns"][:, 0]})
+    if cfg.clip_report:                        # what the resilient aggregation trimmed, per recipient and in-neighbour slot (seed 0)
+        rep = eng.clip_report()
+        sim_data.attrs['clip_report'] = {net: {k: (v[0] if k in ("below", "above", "sender_rate") else v) for k, v in r.items()}
+                                         for net, r in rep.items()}
     if args.get('verbose'):
         for t in range(len(sim_data)):
             print('| Episode: {} | Est. returns: {} | Returns: {} '.format(t, sim_data["Estimated_team_returns"][t],

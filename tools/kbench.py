@@ -4,6 +4,7 @@
     python tools/kbench.py gemm      # layer-1 GEMMs (variant via RCMARL_GEMM=0|1|2)
     python tools/kbench.py k1        # consensus_params at (d,H) = (4,1), (10,4), (18,8)
     python tools/kbench.py k1_ragged # consensus_params_ragged on a degree mix against one masked uniform launch per class
+    python tools/kbench.py clip_counts # the clip report's count entry beside the K1 launch of the same shape
     python tools/kbench.py mid       # mid_fit / consensus_head / mid_value
     python tools/kbench.py rollout_wide  # wide actor: one step of 50 episodes, matrix-core kernel vs plain kernel vs the weight stream
     python tools/kbench.py mb_wide [--hid 64] [--in-dim I --chains 2,8,64,256]   # adversaries beside wide nets: one mini-batch-fit launch
@@ -168,6 +169,52 @@ def k1_cfg5(L):
                                                            H, None, None, st), iters=5, warm=2)
     print("   circulant kernel (G=%s): %9.1f us  %7.1f GB/s (%.1f%% of 8 TB/s)" % (os.environ.get("RCMARL_K1_G", "default"), t,
                                                                                   byts / t / 1e3, byts / t / 1e3 / 80))
+
+
+def clip_counts(L, repeats=5):
+    """rcmarl_consensus_clip_counts beside the K1 call it precedes in the engine, same shape, same buffers, same run: BASELINE
+    configs[3] (N = 256, d = 18, H = 8, S = 16; the critic's and the team-reward net's P_hid) and the k1_cfg5 shape.  The yardstick
+    is the K1 launch the engine takes there (the circulant kernel).  `repeats` timings (HIP events) of each; prints them and one
+    JSON line (median, min, max in us; the ratio of the medians)."""
+    import json
+    st = torch.cuda.current_stream().cuda_stream
+    shapes = [("cfg3_critic", 16, 256, 18, 8, 10680, 20), ("cfg3_tr", 16, 256, 18, 8, 15800, 20)]
+    cfg5_P_hid = (2048 * 512 + 512 + 512 * 512 + 512 + 7) // 8
+    shapes.append(("k1_cfg5", 1, 1024, 66, 32, cfg5_P_hid, 5))
+    out = {"repeats": repeats}
+    for name, S, N, d, H, P_hid, iters in shapes:
+        ldp = pad64(P_hid + 21)
+        msg = torch.randn(S, N, ldp, device="cuda")
+        theta = torch.zeros(S, N, ldp, device="cuda")
+        nbr = torch.tensor([[(i + k) % N for k in range(d)] for i in range(N)], dtype=torch.int32, device="cuda")
+        coop = torch.ones(N, dtype=torch.int32, device="cuda")
+        below = torch.zeros(S, N, d, dtype=torch.int64, device="cuda")
+        above = torch.zeros(S, N, d, dtype=torch.int64, device="cuda")
+        n_scr = L.rcmarl_consensus_clip_counts_scratch(S, N, d, P_hid)
+        scratch = torch.zeros(max(n_scr, 1), dtype=torch.int32, device="cuda")
+        count = lambda: L.rcmarl_consensus_clip_counts(msg.data_ptr(), nbr.data_ptr(), coop.data_ptr(), below.data_ptr(), above.data_ptr(),
+                                                       scratch.data_ptr(), S, N, ldp, P_hid, d, H, d, st)
+        if L.rcmarl_consensus_params_circulant_supported(N, d, H):
+            k1_ = lambda: L.rcmarl_consensus_params_circulant(msg.data_ptr(), theta.data_ptr(), coop.data_ptr(), S, N, ldp, P_hid, d, H,
+                                                              None, None, st)
+        else:
+            k1_ = lambda: L.rcmarl_consensus_params(msg.data_ptr(), theta.data_ptr(), nbr.data_ptr(), coop.data_ptr(), S, N, ldp, P_hid,
+                                                    d, H, None, None, st)
+        res = {}
+        for label, fn in (("k1", k1_), ("clip_counts", count)):
+            ts = sorted(timeit(fn, iters=iters, warm=2) for _ in range(repeats))
+            res[label] = {"median_us": ts[len(ts) // 2], "min_us": ts[0], "max_us": ts[-1]}
+        torch.cuda.synchronize()
+        per_call = int(below.sum().item() + above.sum().item())      # (random messages: the launches must have counted something)
+        res["ratio"] = res["clip_counts"]["median_us"] / res["k1"]["median_us"]
+        res["msg_bytes"] = 4.0 * S * N * P_hid
+        res["scratch_bytes"] = 4 * n_scr
+        out[name] = res
+        assert per_call > 0
+        print("%-12s S=%2d N=%4d d=%2d H=%2d P_hid=%7d  K1 %9.1f us  clip counts %9.1f us  (x%.2f; message matrix %.0f MB -> %.0f GB/s "
+              "algorithmic for the count)" % (name, S, N, d, H, P_hid, res["k1"]["median_us"], res["clip_counts"]["median_us"], res["ratio"],
+                                              res["msg_bytes"] / 1e6, res["msg_bytes"] / res["clip_counts"]["median_us"] / 1e3))
+    print(json.dumps({"kbench": "clip_counts", **out}))
 
 
 def minibatch(L, S=512, N=5, B=3000):
@@ -747,4 +794,4 @@ if __name__ == "__main__":
     L = capi.CLib(os.environ["RCMARL_KBENCH_LIB"]) if os.environ.get("RCMARL_KBENCH_LIB") else capi.load()     # (variant builds)
     what = sys.argv[1] if len(sys.argv) > 1 else "gemm"
     print("== %s  RCMARL_GEMM=%s RCMARL_K1=%s" % (what, os.environ.get("RCMARL_GEMM"), os.environ.get("RCMARL_K1")))
-    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk, "rollout_wide": rollout_wide, "mb_wide": mb_wide, "mb_actor_wide": mb_actor_wide}[what](L)
+    {"gemm": gemm, "k1": k1, "k1_ragged": k1_ragged, "k1_cfg5": k1_cfg5, "clip_counts": clip_counts, "mid": mid, "lattice": lattice, "lattice_ab": lattice_ab, "mid_ab": mid_ab, "minibatch": minibatch, "multi": multi, "wide": wide, "pk": pk, "rollout_wide": rollout_wide, "mb_wide": mb_wide, "mb_actor_wide": mb_actor_wide}[what](L)
