@@ -354,6 +354,17 @@ int rcmarl_minibatch_actor_wide(const float* x, long x_seed_stride, float* theta
                                 const int* agents, int n_adv, const float* act_t, const float* delta, const int* perm, int S,
                                 int N, int B, int in_dim, int hid, int n_actions, int ldp, int ldb, int batch_size, int epochs,
                                 double lr, double beta1, double beta2, double eps, int t0, float* loss_out, void* stream);
+/* The same fit for the widths beyond that layout whose TWO activation images fit the LDS (dz1 is written over a1, as
+ * rcmarl_minibatch_fit_wide2 does for the critic family): argument list, layouts, error codes and semantics are those of
+ * rcmarl_minibatch_actor_wide, the caller-owned `grad` scratch [S][n_adv][ldp] (zeroed by the kernel) included.
+ * rcmarl_minibatch_actor_wide2_supported (host only): 1 exactly where the two-image layout fits and
+ * rcmarl_minibatch_actor_wide_supported answers 0 -- 385 <= hid <= 576 with 2 <= n_actions <= 8, in_dim >= 1, batch_size >= 1;
+ * 0 otherwise, non-positive arguments included.  The two queries never both answer 1. */
+int rcmarl_minibatch_actor_wide2_supported(int in_dim, int hid, int n_actions, int batch_size);
+int rcmarl_minibatch_actor_wide2(const float* x, long x_seed_stride, float* theta, float* adam_m, float* adam_v, float* grad,
+                                 const int* agents, int n_adv, const float* act_t, const float* delta, const int* perm, int S,
+                                 int N, int B, int in_dim, int hid, int n_actions, int ldp, int ldb, int batch_size, int epochs,
+                                 double lr, double beta1, double beta2, double eps, int t0, float* loss_out, void* stream);
 
 /* r_coop[s][b] = sum_{coop n, index order} r[s][b][n]/n_coop   (training/train_agents.py:96-98) */
 int rcmarl_team_reward(const float* r, long seed_stride, const int* coop, int n_coop, float* rcoop, int S,

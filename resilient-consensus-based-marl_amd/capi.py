@@ -151,6 +151,11 @@ SIGNATURES = {
     "rcmarl_minibatch_actor_wide": [c_f32p, c_long, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_int, c_f32p, c_f32p, c_i32p, c_int,
                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double,
                                     C.c_double, C.c_double, c_int, c_f32p, c_stream],
+    # the same argument lists for 385 .. 576 units (two activation images in LDS; the two queries never both answer 1)
+    "rcmarl_minibatch_actor_wide2_supported": [c_int, c_int, c_int, c_int],
+    "rcmarl_minibatch_actor_wide2": [c_f32p, c_long, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_int, c_f32p, c_f32p, c_i32p, c_int,
+                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, c_int, c_f32p, c_stream],
     # src, seed_stride, rcoop, mode, out, S, N, B, ldb, stream
     "rcmarl_gather_agent_major": [c_f32p, c_long, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_stream],
     # src, seed_stride, first, step, n_rows, width, dst, S, stream
@@ -275,7 +280,8 @@ UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_
              "rcmarl_wide_grad_size", "rcmarl_wide_rows_per_chunk", "rcmarl_wide_f16_mode", "rcmarl_wide_set_f16_mode",
              "rcmarl_consensus_params_circulant_supported", "rcmarl_consensus_clip_counts_scratch", "rcmarl_pk_supported", "rcmarl_pk_parts",
              "rcmarl_rollout_wide_supported", "rcmarl_minibatch_fit_wide_supported",
-             "rcmarl_minibatch_fit_wide2_supported", "rcmarl_minibatch_actor_wide_supported"}
+             "rcmarl_minibatch_fit_wide2_supported", "rcmarl_minibatch_actor_wide_supported",
+             "rcmarl_minibatch_actor_wide2_supported"}
 
 # host-only size queries that return long (bytes), not a status: name -> argtypes
 LONG_QUERIES = {

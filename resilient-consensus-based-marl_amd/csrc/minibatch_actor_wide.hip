@@ -19,6 +19,15 @@
 // k_minibatch_train does); a workgroup barrier separates that pass from the next step's loads.
 // Rows >= nb of a short tile carry dz3 = 0, so they add nothing to any gradient; unit columns >= hid of the last tile stay zero;
 // inputs wider than one staged chunk are re-staged wherever they are needed.  Semantics: oracle/mlp_np.fit_actor_ce.
+//
+// Two entry points share the kernel body through a compile-time flag.  rcmarl_minibatch_actor_wide keeps THREE [32][LD] images (a1,
+// a2 / dz2, dz1): widths up to 384.  rcmarl_minibatch_actor_wide2 keeps TWO, dz1 written over a1, as csrc/minibatch_wide2.hip does for
+// the critic family: widths 385 .. 576 (2 * 32 * 577 floats + the staged chunk + dz3 + indices + loss = 157 440 bytes of the 160 KiB).
+// dz1 may take a1's place because in the backward pass through layer 2 the wavefront that owns unit tile `it` is the only reader of
+// a1's columns of that tile: once as a1f (into registers, before the jt loop) and once for lrelu' at the very address the same lane
+// then writes dz1 to; nothing after that phase reads a1 (gb1 and gW1 read dz1 and the staged inputs), and layer 1 of the next row
+// tile rewrites the whole image, the padding columns of the last unit tile included (they stay zero in between: their masked weights
+// make da zero there).
 #include "rcmarl_common.h"
 #include <limits.h>
 
@@ -42,9 +51,10 @@ struct AwArgs {
 };
 
 __host__ __device__ inline int aw_ld(int hid) { return ((hid + 31) & ~31) + 1; }
-// a1 | a2 (dz2) | dz1: [32][LD]; staged inputs [32][AW_XLD]; dz3 [32][8]; row indices[32]; loss[32] (double)
-size_t aw_smem_bytes(int hid) {
-  return sizeof(float) * ((size_t)3 * AW_ROWS * aw_ld(hid) + AW_ROWS * AW_XLD + AW_ROWS * AW_MAX_A) + sizeof(int) * AW_ROWS +
+// a1 | a2 (dz2) | dz1: [32][LD] (`images` = 3), or a1 (dz1) | a2 (dz2) (`images` = 2); staged inputs [32][AW_XLD]; dz3 [32][8];
+// row indices[32]; loss[32] (double)
+size_t aw_smem_bytes(int hid, int images) {
+  return sizeof(float) * ((size_t)images * AW_ROWS * aw_ld(hid) + AW_ROWS * AW_XLD + AW_ROWS * AW_MAX_A) + sizeof(int) * AW_ROWS +
          sizeof(double) * AW_ROWS;
 }
 
@@ -56,6 +66,8 @@ __device__ __forceinline__ float aw_keep(float v, unsigned keep) { return __uint
 // accumulator slot q of a lane in half h holds row aw_drow(q, h) of the 32 x 32 product (column = lane & 31)
 __device__ __forceinline__ int aw_drow(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
 
+// TWO: the two-image layout (dz1 over a1)
+template <bool TWO>
 __global__ __launch_bounds__(AW_THREADS) void k_minibatch_actor_wide(AwArgs m) {
   RCMARL_DYN_SMEM(float, smem);
   const int net = (int)blockIdx.x;
@@ -64,8 +76,8 @@ __global__ __launch_bounds__(AW_THREADS) void k_minibatch_actor_wide(AwArgs m) {
   const NetGeom g = make_geom(in, hid, A);
   float* a1s = smem;                       // [32][LD]
   float* a2s = a1s + AW_ROWS * LD;         // [32][LD]  a2, then dz2 in place
-  float* dz1s = a2s + AW_ROWS * LD;        // [32][LD]
-  float* xs = dz1s + AW_ROWS * LD;         // [32][AW_XLD] staged input chunk
+  float* dz1s = TWO ? a1s : a2s + AW_ROWS * LD;      // [32][LD]  (TWO: a1's image, each element written by the lane that read it last)
+  float* xs = (TWO ? a2s : dz1s) + AW_ROWS * LD;     // [32][AW_XLD] staged input chunk
   float* dz3s = xs + AW_ROWS * AW_XLD;     // [32][8] dLoss/dlogits per row (columns >= A: zero)
   int* idxs = reinterpret_cast<int*>(dz3s + AW_ROWS * AW_MAX_A);      // [32] replay rows of the tile
   double* lossr = reinterpret_cast<double*>(idxs + AW_ROWS);           // [32] (8-byte aligned: an even number of 4-byte words precedes it)
@@ -400,21 +412,32 @@ __global__ __launch_bounds__(AW_THREADS) void k_minibatch_actor_wide(AwArgs m) {
 
 }  // namespace
 
-RCMARL_EXPORT int rcmarl_minibatch_actor_wide_supported(int in_dim, int hid, int n_actions, int batch_size) {
-  if (in_dim <= 0 || hid <= 0 || hid > AW_MAX_HID || n_actions < 2 || n_actions > AW_MAX_A || batch_size <= 0) return 0;
-  if (((long)in_dim + hid + 2 + n_actions) * hid + n_actions > (long)INT_MAX) return 0;      // parameter offsets are ints
-  return aw_smem_bytes(hid) <= AW_LDS_LIMIT ? 1 : 0;
+static bool aw_shape_ok(int in_dim, int hid, int n_actions, int batch_size) {
+  if (in_dim <= 0 || hid <= 0 || hid > AW_MAX_HID || n_actions < 2 || n_actions > AW_MAX_A || batch_size <= 0) return false;
+  return ((long)in_dim + hid + 2 + n_actions) * hid + n_actions <= (long)INT_MAX;      // parameter offsets are ints
 }
 
-RCMARL_EXPORT int rcmarl_minibatch_actor_wide(const float* x, long x_seed_stride, float* theta, float* adam_m, float* adam_v,
-                                              float* grad, const int* agents, int n_adv, const float* act_t, const float* delta,
-                                              const int* perm, int S, int N, int B, int in_dim, int hid, int n_actions, int ldp,
-                                              int ldb, int batch_size, int epochs, double lr, double beta1, double beta2, double eps,
-                                              int t0, float* loss_out, void* stream) {
+RCMARL_EXPORT int rcmarl_minibatch_actor_wide_supported(int in_dim, int hid, int n_actions, int batch_size) {
+  if (!aw_shape_ok(in_dim, hid, n_actions, batch_size)) return 0;
+  return aw_smem_bytes(hid, 3) <= AW_LDS_LIMIT ? 1 : 0;
+}
+
+// the widths beyond the three-image layout that the two-image layout holds: never 1 together with the query above
+RCMARL_EXPORT int rcmarl_minibatch_actor_wide2_supported(int in_dim, int hid, int n_actions, int batch_size) {
+  if (!aw_shape_ok(in_dim, hid, n_actions, batch_size)) return 0;
+  return aw_smem_bytes(hid, 3) > AW_LDS_LIMIT && aw_smem_bytes(hid, 2) <= AW_LDS_LIMIT ? 1 : 0;
+}
+
+template <bool TWO>
+static int aw_run(const float* x, long x_seed_stride, float* theta, float* adam_m, float* adam_v, float* grad, const int* agents,
+                  int n_adv, const float* act_t, const float* delta, const int* perm, int S, int N, int B, int in_dim, int hid,
+                  int n_actions, int ldp, int ldb, int batch_size, int epochs, double lr, double beta1, double beta2, double eps, int t0,
+                  float* loss_out, void* stream) {
   if (!x || !theta || !adam_m || !adam_v || !grad || !agents || !act_t || !delta || n_adv <= 0 || S <= 0 || N <= 0 || B <= 0 ||
       in_dim <= 0 || hid <= 0 || n_actions <= 0 || batch_size <= 0 || epochs <= 0 || t0 < 0 || ldp <= 0 || (ldp & 63) || ldb < B)
     return RCMARL_ERR_ARG;
-  if (!rcmarl_minibatch_actor_wide_supported(in_dim, hid, n_actions, batch_size)) return RCMARL_ERR_UNSUPPORTED;
+  if (!(TWO ? rcmarl_minibatch_actor_wide2_supported : rcmarl_minibatch_actor_wide_supported)(in_dim, hid, n_actions, batch_size))
+    return RCMARL_ERR_UNSUPPORTED;
   if (((long)in_dim + hid + 2 + n_actions) * hid + n_actions > (long)ldp) return RCMARL_ERR_ARG;      // the net does not fit its row
   if ((long)S * n_adv > (long)INT_MAX) return RCMARL_ERR_ARG;
   AwArgs m{};
@@ -424,8 +447,26 @@ RCMARL_EXPORT int rcmarl_minibatch_actor_wide(const float* x, long x_seed_stride
   m.bs = batch_size < B ? batch_size : B; m.epochs = epochs; m.t0 = t0;
   m.lr = lr; m.beta1 = beta1; m.beta2 = beta2;      // alpha and (1 - beta) are formed in double, then rounded (Keras/TF2 order)
   m.one_m_b1 = (float)(1.0 - beta1); m.one_m_b2 = (float)(1.0 - beta2); m.eps = (float)eps;
-  const size_t smem = aw_smem_bytes(hid);
-  if (!rc_want_lds(k_minibatch_actor_wide, smem, 48 * 1024)) return RCMARL_ERR_LAUNCH;
-  RCMARL_LAUNCH(k_minibatch_actor_wide, dim3(S * n_adv), dim3(AW_THREADS), smem, stream, m);
+  const size_t smem = aw_smem_bytes(hid, TWO ? 2 : 3);
+  if (!rc_want_lds(k_minibatch_actor_wide<TWO>, smem, 48 * 1024)) return RCMARL_ERR_LAUNCH;
+  RCMARL_LAUNCH(k_minibatch_actor_wide<TWO>, dim3(S * n_adv), dim3(AW_THREADS), smem, stream, m);
   return rcmarl_check_launch();
+}
+
+RCMARL_EXPORT int rcmarl_minibatch_actor_wide(const float* x, long x_seed_stride, float* theta, float* adam_m, float* adam_v,
+                                              float* grad, const int* agents, int n_adv, const float* act_t, const float* delta,
+                                              const int* perm, int S, int N, int B, int in_dim, int hid, int n_actions, int ldp,
+                                              int ldb, int batch_size, int epochs, double lr, double beta1, double beta2, double eps,
+                                              int t0, float* loss_out, void* stream) {
+  return aw_run<false>(x, x_seed_stride, theta, adam_m, adam_v, grad, agents, n_adv, act_t, delta, perm, S, N, B, in_dim, hid, n_actions,
+                       ldp, ldb, batch_size, epochs, lr, beta1, beta2, eps, t0, loss_out, stream);
+}
+
+RCMARL_EXPORT int rcmarl_minibatch_actor_wide2(const float* x, long x_seed_stride, float* theta, float* adam_m, float* adam_v,
+                                               float* grad, const int* agents, int n_adv, const float* act_t, const float* delta,
+                                               const int* perm, int S, int N, int B, int in_dim, int hid, int n_actions, int ldp,
+                                               int ldb, int batch_size, int epochs, double lr, double beta1, double beta2, double eps,
+                                               int t0, float* loss_out, void* stream) {
+  return aw_run<true>(x, x_seed_stride, theta, adam_m, adam_v, grad, agents, n_adv, act_t, delta, perm, S, N, B, in_dim, hid, n_actions,
+                      ldp, ldb, batch_size, epochs, lr, beta1, beta2, eps, t0, loss_out, stream);
 }

@@ -70,7 +70,7 @@ class EngineConfig:
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
                  local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID, adv_wide2="auto",
-                 w1_tiled="auto", fit_from_live="auto", clip_report=False):
+                 w1_tiled="auto", fit_from_live="auto", clip_report=False, adv_actor="refuse"):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -95,6 +95,14 @@ class EngineConfig:
         if not any(adv_wide2 is v for v in (True, False)) and adv_wide2 != "auto":
             raise ValueError("adv_wide2 must be 'auto', True or False")
         self.adv_wide2 = adv_wide2
+        # a wide actor beside Greedy / Malicious / Faulty agents: "refuse" (the combination raises below) | "auto" (each phase-III
+        # fit of the adversaries' actors is ONE launch -- rcmarl_minibatch_actor_wide up to 384 units, rcmarl_minibatch_actor_wide2 from
+        # 385 to 576 -- from engine_adversaries.ACTOR_WIDE_MIN_CHAINS / ACTOR_WIDE2_MIN_CHAINS chains on, the launch-per-step loop
+        # below and for a shape neither query serves) | "launch" (the launch wherever a query answers 1) | "loop" (always the loop).
+        # No effect with a 20-unit actor.
+        if adv_actor not in ("refuse", "auto", "launch", "loop"):
+            raise ValueError("adv_actor must be 'refuse', 'auto', 'launch' or 'loop'")
+        self.adv_actor = adv_actor
         # local fits of the 20-unit nets on the lattice path: the fp32 W1 of the message lives in accumulator-tile order between the
         # SGD steps of a fit (rcmarl_layer1_backward_sgd_lattice_tiled): "auto" (see W1_TILED_AUTO) | True | False
         if not any(w1_tiled is v for v in (True, False)) and w1_tiled != "auto":
@@ -141,9 +149,10 @@ class EngineConfig:
         if self.tr_hid < 1:
             raise ValueError("tr_hid must be positive")
         if self.actor_hid != HID:
-            if any(lab != COOP for lab in self.agent_label):
+            if self.adv_actor == "refuse" and any(lab != COOP for lab in self.agent_label):
                 raise ValueError("a wide actor (actor_hid = %d) needs an all-cooperative team: the Greedy / Malicious / Faulty agents' "
-                                 "mini-batch chains (csrc/minibatch_fit.hip) are compiled for 20 units" % self.actor_hid)
+                                 "mini-batch chains (csrc/minibatch_fit.hip) are compiled for 20 units (adv_actor='auto' routes their "
+                                 "actor fits to the wide-actor kernels)" % self.actor_hid)
             if not self.regular:
                 raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit actor (actor_hid = %d)"
                                  % self.actor_hid)

@@ -30,6 +30,14 @@ local-fit step on 32 rows, chains one after the other in a Python loop): correct
 a counter-based stream (csrc/shuffle.hip, generated on the device for all seeds at once; the oracle
 states the same definition), consumed in the reference's call order so that oracle and engine stay in
 lock step.
+
+The actor fit (phase III, fit(batch_size=200, epochs=1) with Adam on the rows of the last n_ep_fixed episodes, weighted by the TD
+error of the adversary's own critic) goes by the ACTOR's width: 20 units -- ONE rcmarl_minibatch_actor launch; any other width
+(EngineConfig.adv_actor, "refuse" by default: the combination then raises at construction) -- ONE rcmarl_minibatch_actor_wide launch
+for all (seed, adversary) chains up to 384 units, ONE rcmarl_minibatch_actor_wide2 launch from 385 to 576 (csrc/minibatch_actor_wide.hip,
+one workgroup per chain), or the loop: chain after chain on (seed, agent) = (1, 1) views, the nine launches of the wide Adam step
+(RPBCACEngine._actor_step_wide) per mini-batch on the gathered rows.  adv_actor="auto" takes the launch from ACTOR_WIDE_MIN_CHAINS /
+ACTOR_WIDE2_MIN_CHAINS chains on, "launch" wherever a query answers 1, "loop" never; beyond 576 units it is always the loop.
 """
 import os
 
@@ -46,6 +54,19 @@ FIT_BATCH, FIT_EPOCHS, ACTOR_BATCH = 32, 10, 200
 # loop's 117 ms per chain (they cross at 3 chains), 1410 / 1430 ms for 2 / 8 chains of 2048 inputs against 222 ms per chain (they
 # cross at 7): from 7 chains on the launch is the faster one at both ends.
 WIDE2_MIN_CHAINS = 7
+# The same rule for the adversaries' ACTOR fits beside a wide actor under EngineConfig(adv_actor="auto"): fewest chains (seeds x
+# adversaries) from which the one launch (rcmarl_minibatch_actor_wide up to 384 units, rcmarl_minibatch_actor_wide2 from 385 to 576) is
+# faster than the nine-launch composition run chain after chain, at BOTH ends of the kernel's width range.
+# Measured on an MI355X at 10 inputs, B = 1000 (five mini-batches of 200 rows), 5 actions, 1 / 2 / 4 / 8 / 16 chains
+# (tools/kbench.py mb_actor_wide, docs/history/r16.md has the table).  The launch's time hardly moves with the chain count, the
+# composition's is its per-chain time times the count.  rcmarl_minibatch_actor_wide: 64 units 0.74 .. 0.77 ms against 0.78 ms per
+# chain (the launch wins from 1 chain on), 384 units 7.33 .. 7.36 ms for 1 .. 8 chains against 1.39 ms per chain (0.76 x at 4 chains,
+# 1.51 x at 8; they cross between 5 and 6): from 6 chains on the launch is the faster one at both ends.
+# rcmarl_minibatch_actor_wide2: 416 units 9.43 .. 9.46 ms for 1 .. 8 chains against 1.43 ms per chain (they cross at 7), 576 units
+# 16.8 ms for 8 chains and 17.9 ms for 16 against 1.69 ms per chain (0.81 x at 8 chains, 1.52 x at 16; with the launch's time
+# interpolated between those two they cross between 10 and 11): from 11 chains on at both ends.
+ACTOR_WIDE_MIN_CHAINS = 6
+ACTOR_WIDE2_MIN_CHAINS = 11
 
 
 class AdversaryPath:
@@ -358,6 +379,8 @@ class AdversaryPath:
         e._value("s", own, "critic", e.ybuf["v_cur_adv"], nl, row0, value_f32=True)
         L.rcmarl_td_error(e.ybuf["r_own"].data_ptr(), e.ybuf["v_next_adv"].data_ptr(), e.ybuf["v_cur_adv"].data_ptr(),
                           e.cfg.gamma, e.ybuf["delta_adv"].data_ptr(), S * N * e.ldb, e.stream)
+        if e.actor_wide:
+            return self._actor_fit_wide(nl, row0, perms)
         sptr, sstride = e._x("s", row0)
         L.rcmarl_minibatch_actor(sptr, sstride, e.theta["actor"].data_ptr(), e.adam_m.data_ptr(), e.adam_v.data_ptr(),
                                  self.adv_t.data_ptr(), len(self.adv), e.ybuf["act_t"].data_ptr(),
@@ -365,6 +388,87 @@ class AdversaryPath:
                                  e.in_c, HID, e.cfg.n_actions, e.ldp["actor"], e.ldb, ACTOR_BATCH, 1, e.cfg.slow_lr,
                                  0.9, 0.999, 1e-7, self.adam_t, e.loss["actor"].data_ptr(), e.stream)
         self.adam_t += (nl + ACTOR_BATCH - 1) // ACTOR_BATCH
+
+    # -- phase III beside a wide actor (EngineConfig.adv_actor) ------------------------------------------------
+    def actor_route(self):
+        """Where a phase-III fit of the adversaries' wide actors goes: the name of the one-launch entry point whose query serves
+        the shape -- under adv_actor="auto" only from its measured chain count on -- or None, the launch-per-step loop."""
+        e, L = self.e, self.e.lib
+        mode = e.cfg.adv_actor
+        if mode == "loop":
+            return None
+        for name, min_chains in (("rcmarl_minibatch_actor_wide", ACTOR_WIDE_MIN_CHAINS), ("rcmarl_minibatch_actor_wide2", ACTOR_WIDE2_MIN_CHAINS)):
+            if hasattr(L, name + "_supported") and getattr(L, name + "_supported")(e.in_c, e.hid["actor"], e.cfg.n_actions, ACTOR_BATCH) == 1:
+                return None if mode == "auto" and e.S * len(self.adv) < min_chains else name
+        return None
+
+    def _actor_fit_wide(self, nl, row0, perms):
+        """fit(batch_size=200, epochs=1) of every adversary's wide actor on the last nl rows, weighted by delta_adv: ONE launch for
+        all (seed, adversary) chains (actor_route), else the loop.  Either way the Adam step count advances by ceil(nl / 200)."""
+        e = self.e
+        name = self.actor_route()
+        if name is None:
+            self._actor_fit_loop(nl, row0, perms)
+        else:
+            if getattr(self, "_actor_grad", None) is None:         # gradient sums of a mini-batch, one row per chain (zeroed by the kernel)
+                self._actor_grad = torch.zeros(e.S, len(self.adv), e.ldp["actor"], dtype=torch.float32, device=e.dev)
+            sptr, sstride = e._x("s", row0)
+            getattr(e.lib, name)(sptr, sstride, e.theta["actor"].data_ptr(), e.adam_m.data_ptr(), e.adam_v.data_ptr(),
+                                 self._actor_grad.data_ptr(), self.adv_t.data_ptr(), len(self.adv), e.ybuf["act_t"].data_ptr(),
+                                 e.ybuf["delta_adv"].data_ptr(), None if perms is None else perms.data_ptr(), e.S, e.N, nl, e.in_c,
+                                 e.hid["actor"], e.cfg.n_actions, e.ldp["actor"], e.ldb, ACTOR_BATCH, 1, e.cfg.slow_lr, 0.9, 0.999, 1e-7,
+                                 self.adam_t, e.loss["actor"].data_ptr(), e.stream)
+        self.adam_t += (nl + ACTOR_BATCH - 1) // ACTOR_BATCH
+
+    def _actor_fit_loop(self, nl, row0, perms):
+        """The same fit one chain after the other on (seed, agent) = (1, 1) views: per mini-batch the permuted rows are gathered and
+        the nine launches of RPBCACEngine._actor_step_wide run on them -- the step size of Adam step t0 + k, the mask all ones, the
+        head weighting the gradient by delta_adv / nb; the first-epoch loss is the length-weighted mean of the batch losses
+        (single.RowOps.minibatch_actor states the same composition).  Correct and slow: it serves the shapes neither one-launch kernel
+        holds and the chain counts at which one compute unit per chain loses to the whole chip per step.  The activation scratch is
+        the cooperative Adam step's (dead by now; a mini-batch is at most n_last rows)."""
+        e, L = self.e, self.e.lib
+        c, hid, in_dim, A, ldp, st = e.cfg, e.hid["actor"], e.in_c, e.cfg.n_actions, e.ldp["actor"], e.stream
+        o_b1, o_W2, o_b2 = e._wide_offsets("actor")
+        o_W3 = o_b2 + hid
+        if e.wa_alias:
+            e.a2_cached = False                        # (the wide critic's w_a2 holds actor activations from here on)
+        if getattr(self, "_actor_one", None) is None:
+            self._actor_one = torch.ones(1, dtype=torch.int32, device=e.dev)
+            self._actor_loss1 = torch.zeros(1, dtype=torch.float32, device=e.dev)
+        a1, a2, dz, dz3, lp = (t.data_ptr() for t in (e.wa_a1, e.wa_a2, e.wa_dz, e.wa_dz3, e.wa_losspart))
+        one, loss1 = self._actor_one.data_ptr(), self._actor_loss1.data_ptr()
+        b1, b2 = 0.9, 0.999
+        omb1, omb2, epsf = float(np.float32(1 - b1)), float(np.float32(1 - b2)), float(np.float32(1e-7))
+        X, act, delta = e.rp["s"], e.ybuf["act_t"], e.ybuf["delta_adv"]
+        natural = torch.arange(nl, device=e.dev) if perms is None else None
+        for s_ in range(e.S):
+            for q, ag in enumerate(self.adv):
+                row = (s_ * e.N + ag) * ldp
+                th, mp, vp = (t.data_ptr() + 4 * row for t in (e.theta["actor"], e.adam_m, e.adam_v))
+                idx = natural if perms is None else perms[s_, q, 0].long()
+                Xp = X[s_, row0:row0 + nl].index_select(0, idx).contiguous()          # [nl][in_dim]: batches are row slices now
+                yp = act[s_, ag, :nl].index_select(0, idx).contiguous()
+                wp = delta[s_, ag, :nl].index_select(0, idx).contiguous()
+                first = torch.zeros(1, dtype=torch.float32, device=e.dev)
+                for k, lo in enumerate(range(0, nl, ACTOR_BATCH)):
+                    nb = min(ACTOR_BATCH, nl - lo)
+                    ldn = (nb + 63) // 64 * 64
+                    t = self.adam_t + k + 1
+                    alpha = float(np.float32(c.slow_lr * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)))
+                    adam = (alpha, omb1, omb2, epsf, st)
+                    xb, yb, wb = Xp.data_ptr() + 4 * lo * in_dim, yp.data_ptr() + 4 * lo, wp.data_ptr() + 4 * lo
+                    L.rcmarl_dense_forward(xb, 0, 0, 1, in_dim, th, 0, o_b1, a1, 1, 1, nb, in_dim, hid, ldp, ldn, st)
+                    L.rcmarl_dense_forward(a1, hid * ldn, hid * ldn, 0, ldn, th, o_W2, o_b2, a2, 1, 1, nb, hid, hid, ldp, ldn, st)
+                    L.rcmarl_wide_actor_head(a2, th, yb, wb, nb, dz3, lp, 1, 1, nb, in_dim, hid, A, ldp, ldn, st)
+                    L.rcmarl_dense_backward_data(dz3, th, o_W3, a2, dz, 1, 1, nb, hid, A, ldp, ldn, st)
+                    L.rcmarl_dense_backward_adam(a2, hid * ldn, hid * ldn, 0, ldn, dz3, th, mp, vp, o_W3, one, 1, 1, nb, hid, A, ldp, ldn, *adam)
+                    L.rcmarl_dense_backward_data(dz, th, o_W2, a1, a2, 1, 1, nb, hid, hid, ldp, ldn, st)
+                    L.rcmarl_dense_backward_adam(a1, hid * ldn, hid * ldn, 0, ldn, dz, th, mp, vp, o_W2, one, 1, 1, nb, hid, hid, ldp, ldn, *adam)
+                    L.rcmarl_dense_backward_adam(xb, 0, 0, 1, in_dim, a2, th, mp, vp, 0, one, 1, 1, nb, in_dim, hid, ldp, ldn, *adam)
+                    L.rcmarl_wide_actor_small_adam(a2, dz, dz3, lp, th, mp, vp, one, loss1, 1, 1, nb, in_dim, hid, A, ldp, ldn, *adam)
+                    first += self._actor_loss1 * float(nb)               # Keras History: sample-weighted mean of the batch losses
+                e.loss["actor"][s_, ag] = first[0] / float(nl)
 
 
 def attach(eng):

@@ -14,6 +14,8 @@ Extra (optional) ``args`` keys on top of the reference's (main.py:26-44):
   verbose    print one line per episode like the reference (:174)
   clip_report  any truthy value: count what the resilient aggregation trims (EngineConfig.clip_report); the returned DataFrame
              then carries ``attrs['clip_report']`` = {net: {below, above, steps, P_hid, in_nodes, sender_rate}} of the run
+  adv_actor  'auto' (default) | 'launch' | 'loop' | 'refuse': how Greedy / Malicious / Faulty agents' actor fits run when the
+             models' actors are wider than 20 units (EngineConfig.adv_actor)
 """
 import numpy as np
 import pandas as pd
@@ -51,7 +53,8 @@ def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
                        buffer_size=args['buffer_size'], common_reward=_truthy(args['common_reward']), nrow=env.nrow,
                        ncol=env.ncol, n_seeds=1, rng_mode=args.get('rng_mode', 'numpy'),
                        scaling=bool(getattr(env, 'scaling', not np.isscalar(env.mean_state))),
-                       randomize_state=env.randomize_state, clip_report=_truthy(args.get('clip_report')))
+                       randomize_state=env.randomize_state, clip_report=_truthy(args.get('clip_report')),
+                       adv_actor=args.get('adv_actor', 'auto'))
     lib, device = engine_hook if engine_hook is not None else (None, "cuda")
     eng = RPBCACEngine(cfg, seeds=[int(args.get('random_seed', 0))], device=device, lib=lib)
     # ---- agents -> stacked parameter matrices

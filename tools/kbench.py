@@ -741,22 +741,24 @@ def mb_wide(L, N=5, B=2000, epochs=10, bs=32):
 
 
 def mb_actor_wide(L, N=16, B=1000, bs=200, in_dim=10, A=5, lr=0.002):
-    """The adversaries' actor fit(batch_size=200, epochs=1) of a wide actor: ONE rcmarl_minibatch_actor_wide launch over all chains
-    against the nine launches of the wide Adam step (engine._actor_step_wide) once per mini-batch on 200 gathered rows of a
-    (seed, agent) = (1, 1) view, chain after chain; hid 64 and 384, 1 and 16 chains (adversaries of one seed).
+    """The adversaries' actor fit(batch_size=200, epochs=1) of a wide actor: ONE rcmarl_minibatch_actor_wide (hid 64 and 384) or
+    rcmarl_minibatch_actor_wide2 (hid 416, 512 and 576) launch over all chains against the nine launches of the wide Adam step
+    (engine._actor_step_wide) once per mini-batch on 200 gathered rows of a (seed, agent) = (1, 1) view, chain after chain; 1, 2, 4, 8
+    and 16 chains (adversaries of one seed).  engine_adversaries.ACTOR_WIDE_MIN_CHAINS / ACTOR_WIDE2_MIN_CHAINS come from this table.
 
         python tools/kbench.py mb_actor_wide"""
     st = torch.cuda.current_stream().cuda_stream
     steps, ldb, ldn = (B + bs - 1) // bs, pad64(B), pad64(bs)
     p = lambda t: t.data_ptr()
     z = lambda *s: torch.zeros(*s, device="cuda")
-    for hid in (64, 384):
+    for hid in (64, 384, 416, 512, 576):
         o_b1 = in_dim * hid
         o_W2 = o_b1 + hid
         o_b2 = o_W2 + hid * hid
         o_W3 = o_b2 + hid
         ldp = pad64(o_W3 + hid * A + A)
-        assert L.rcmarl_minibatch_actor_wide_supported(in_dim, hid, A, bs) == 1
+        entry = "rcmarl_minibatch_actor_wide" if hid <= 384 else "rcmarl_minibatch_actor_wide2"
+        assert getattr(L, entry + "_supported")(in_dim, hid, A, bs) == 1
         # the yardstick: one mini-batch step of one chain
         th, m, v = torch.empty(1, 1, ldp, device="cuda").uniform_(-0.1, 0.1), z(1, 1, ldp), z(1, 1, ldp)
         xb, act, dl = torch.randn(bs, in_dim, device="cuda"), torch.randint(0, A, (1, 1, ldn), device="cuda").float(), torch.randn(1, 1, ldn, device="cuda")
@@ -776,18 +778,18 @@ def mb_actor_wide(L, N=16, B=1000, bs=200, in_dim=10, A=5, lr=0.002):
         t_step = timeit(step, iters=200, warm=20)
         print("nine-launch composition, in=%d hid=%d: %7.1f us per mini-batch step of %d rows" % (in_dim, hid, t_step, bs), flush=True)
         x = torch.randn(1, B, in_dim, device="cuda")
-        for chains in (1, 16):
+        for chains in (1, 2, 4, 8, 16):
             assert chains <= N
             theta, mm, vv, grad = torch.empty(1, N, ldp, device="cuda").uniform_(-0.1, 0.1), z(1, N, ldp), z(1, N, ldp), z(1, chains, ldp)
             acts, delta = torch.randint(0, A, (1, N, ldb), device="cuda").float(), torch.randn(1, N, ldb, device="cuda")
             agents = torch.arange(chains, dtype=torch.int32, device="cuda")
             perm = torch.stack([torch.randperm(B, device="cuda") for _ in range(chains)]).to(torch.int32).reshape(1, chains, 1, B).contiguous()
-            t = timeit(lambda: L.rcmarl_minibatch_actor_wide(p(x), B * in_dim, p(theta), p(mm), p(vv), p(grad), p(agents), chains, p(acts),
-                                                             p(delta), p(perm), 1, N, B, in_dim, hid, A, ldp, ldb, bs, 1, lr, 0.9, 0.999, 1e-7,
-                                                             0, None, st), iters=20, warm=3)
+            t = timeit(lambda: getattr(L, entry)(p(x), B * in_dim, p(theta), p(mm), p(vv), p(grad), p(agents), chains, p(acts),
+                                                 p(delta), p(perm), 1, N, B, in_dim, hid, A, ldp, ldb, bs, 1, lr, 0.9, 0.999, 1e-7,
+                                                 0, None, st), iters=20, warm=3)
             loop = t_step * steps * chains
-            print("hid=%3d %2d chains x %d steps: ONE rcmarl_minibatch_actor_wide launch %9.1f us; the composition's %d x %d steps %9.1f us; "
-                  "composition / launch = %.2f" % (hid, chains, steps, t, chains, steps, loop, loop / t), flush=True)
+            print("hid=%3d %2d chains x %d steps: ONE %s launch %9.1f us; the composition's %d x %d steps %9.1f us; "
+                  "composition / launch = %.2f" % (hid, chains, steps, entry, t, chains, steps, loop, loop / t), flush=True)
 
 
 if __name__ == "__main__":
