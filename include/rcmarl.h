@@ -519,6 +519,30 @@ int rcmarl_wide_consensus_head(const float* phi, const float* theta, const float
 int rcmarl_wide_consensus_head_nrm(const float* phi, const float* nparts, int n_parts, const float* theta, const float* msg,
                                    const int* nbr, const int* coop, float* hmat, float* hb, float* est, float* ebuf, float* grads,
                                    float* agg_out, int S, int N, int B, int in_dim, int hid, int ldp, int ldb, int d, int H, void* stream);
+/* rcmarl_wide_consensus_head (estimate consensus, agg_in == NULL) on an IRREGULAR in-graph, any hidden width: graph, order[] and
+ * classes as rcmarl_consensus_params_ragged (`classes` is HOST memory, read during the call only).  Per listed agent i with its own
+ * d_i = nbr_off[i+1] - nbr_off[i] (the d of its class) and the H of its class:
+ *   V_m[b] = phi[:, b] . W3(msg[nbr_idx[nbr_off[i] + m]]) + b3(..) for m < d_i, V_live from theta[i];  agg = resilient aggregate over
+ *   m < d_i (own value in slot 0);  e = (agg - V_live) / (|phi|^2 + 1);  ebuf[s][i][b] = e;  grads[s][i][0..hid] = [sum_b e phi | sum_b e].
+ * ONE fused kernel (gather + skinny GEMM on v_mfma_f32_32x32x2_f32 + selection + residual) per 32 classes, then one launch for
+ * grads: no hmat / hb / est scratch.  Nothing else is written: no row of an agent that is not in order[first .. first + count) of a
+ * class, no column b >= B, no slot of est_dbg beyond d_i.
+ *   nparts (optional): |phi|^2 per replay row as n_parts parts nparts[s][n][n_parts][ldb], summed in the order of
+ *     rcmarl_wide_consensus_head_nrm; NULL: accumulated in the same pass over phi as the estimates (phi is read once)
+ *   agg_out (optional) [S][N][ldb];  est_dbg (optional, tests) [S][N][lde][ldb]: slots m < d_i the neighbours' estimates, slot d_i
+ *     the live head, lde >= max d + 1
+ * ORDER of an estimate: accumulator from zero, k-pairs (0,1), (2,3), .. ascending through one accumulator, zero padding beyond hid,
+ * b3 added afterwards -- on a regular graph est_dbg and agg_out carry the bits of rcmarl_wide_consensus_head (a zero's sign among
+ * tied +-0 may differ, as for rcmarl_consensus_params_ragged).  An agent's outputs do not depend on the other agents or classes of
+ * the call, on S, or on the other replay rows; the same call gives the same bits.  No allocation, no synchronisation: safe inside
+ * a captured graph.  Any hid >= 1, d_i >= 1; rcmarl_wide_consensus_head_ragged_supported(hid, d_max) (host-only) says whether the
+ * kernel's LDS tile takes in-neighbourhoods up to d_max (66 and beyond: yes), else RCMARL_ERR_UNSUPPORTED before any HIP call. */
+int rcmarl_wide_consensus_head_ragged_supported(int hid, int d_max);
+int rcmarl_wide_consensus_head_ragged(const float* phi, const float* nparts, int n_parts, const float* theta, const float* msg,
+                                      const int* nbr_off, const int* nbr_idx, const int* order,
+                                      const rcmarl_ragged_class* classes, int n_classes, float* ebuf, float* grads,
+                                      float* agg_out, float* est_dbg, int lde, int S, int N, int B, int in_dim, int hid, int ldp,
+                                      int ldb, void* stream);
 /* W3 += grads[0..hid)/B, b3 += grads[hid]/B (cooperative agents) */
 int rcmarl_wide_head_apply(const float* grads, float* theta, const int* coop, int S, int N, int B, int in_dim, int hid,
                            int ldp, void* stream);

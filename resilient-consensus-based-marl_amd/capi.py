@@ -238,6 +238,12 @@ SIGNATURES = {
     # phi, nparts, n_parts, theta, msg, nbr, coop, hmat, hb, est, ebuf, grads, agg_out, S, N, B, in_dim, hid, ldp, ldb, d, H, stream
     "rcmarl_wide_consensus_head_nrm": [c_f32p, c_f32p, c_int, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                        c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_stream],
+    # the wide head on an irregular graph (csrc/wide_head_ragged.hip): hid, d_max -> 0 / 1
+    "rcmarl_wide_consensus_head_ragged_supported": [c_int, c_int],
+    # phi, nparts, n_parts, theta, msg, nbr_off, nbr_idx, order, classes (host array of RaggedClass), n_classes, ebuf, grads, agg_out,
+    # est_dbg, lde, S, N, B, in_dim, hid, ldp, ldb, stream
+    "rcmarl_wide_consensus_head_ragged": [c_f32p, c_f32p, c_int, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p, c_int, c_f32p,
+                                          c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_stream],
     # vpart, theta, aux, gamma, mode, out, dzv, losspart, S, N, B, in_dim, hid, ldp, ldb, stream
     "rcmarl_pk_head": [c_f32p, c_f32p, c_f32p, c_float, c_int, c_f32p, c_u8p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                        c_stream],
@@ -281,7 +287,7 @@ UNCHECKED = {"rcmarl_abi_version", "rcmarl_mb_job_layout", "rcmarl_ragged_class_
              "rcmarl_consensus_params_circulant_supported", "rcmarl_consensus_clip_counts_scratch", "rcmarl_pk_supported", "rcmarl_pk_parts",
              "rcmarl_rollout_wide_supported", "rcmarl_minibatch_fit_wide_supported",
              "rcmarl_minibatch_fit_wide2_supported", "rcmarl_minibatch_actor_wide_supported",
-             "rcmarl_minibatch_actor_wide2_supported"}
+             "rcmarl_minibatch_actor_wide2_supported", "rcmarl_wide_consensus_head_ragged_supported"}
 
 # host-only size queries that return long (bytes), not a status: name -> argtypes
 LONG_QUERIES = {

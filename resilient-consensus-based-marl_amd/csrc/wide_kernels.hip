@@ -23,6 +23,7 @@
 // (W dz) and backward-weights (x^T dz^T) without materialising a transpose.
 #include "rcmarl_common.h"
 #include "rcmarl_lattice.h"
+#include "rcmarl_wide_rows.h"
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
@@ -499,60 +500,7 @@ __global__ __launch_bounds__(256) void k_whead_fit_cols(const float* __restrict_
   if (threadIdx.x == 0) losspart[((long)s * N + i) * nchunk + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// row passes: one wavefront per feature row j (contiguous over b), results to grads[s][n][...]
-// grads record per (seed, agent): [gW3 (hid) | gb3 | gb2 (hid) | gb1 (hid)]
-__host__ __device__ static inline int w_grad_size(int hid) { return 3 * hid + 1; }
-
-enum { WROW_FIT = 0, WROW_SUM = 1, WROW_DOT = 2 };
-
-// FIT: gW3[j] = sum_b a2[j][b] dz3[b];  dz2[j][b] = W3[j] dz3[b] lrelu'(a2[j][b]) (in place);  gb2[j] = sum_b dz2;
-//      row j == hid: gb3 = sum_b dz3[b]
-// SUM: out[off + j] = sum_b act[j][b]
-// DOT: out[j] = sum_b act[j][b] vec[b];  row j == hid: out[hid] = sum_b vec[b]
-template <int MODE>
-__global__ __launch_bounds__(256) void k_wrows(float* __restrict__ act, const float* __restrict__ vec,
-                                               const float* __restrict__ theta, const int* __restrict__ coop,
-                                               float* __restrict__ grads, int out_off, int N, int B, int in_dim, int hid,
-                                               int ldp, int ldb) {
-  const int s = blockIdx.z, i = blockIdx.y, j = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
-  const int nrows = (MODE == WROW_SUM) ? hid : hid + 1;
-  if (j >= nrows) return;
-  if (coop && !coop[i]) return;
-  float* __restrict__ gr = grads + ((long)s * N + i) * w_grad_size(hid);
-  const float* __restrict__ v = vec ? vec + ((long)s * N + i) * ldb : nullptr;
-  if (j == hid) {                                   // the bias of the head: plain sum of vec
-    float acc = 0.f;
-    for (int b = l; b < B; b += 64) acc += v[b];
-    acc = rc_wave_sum(acc);
-    if (l == 0) gr[hid] = acc;
-    return;
-  }
-  float* __restrict__ row = act + (((long)s * N + i) * hid + j) * ldb;
-  if (MODE == WROW_FIT) {
-    const float w3 = theta[((long)s * N + i) * ldp + make_geom(in_dim, hid, 1).o_W3 + j];
-    float gw = 0.f, gb = 0.f;
-    for (int b = l; b < B; b += 64) {
-      const float a2 = row[b], dv = v[b];
-      gw = fmaf(a2, dv, gw);
-      const float dz = dv * w3 * rc_lrelu_grad_from_act(a2);
-      row[b] = dz;
-      gb += dz;
-    }
-    gw = rc_wave_sum(gw);
-    gb = rc_wave_sum(gb);
-    if (l == 0) { gr[j] = gw; gr[hid + 1 + j] = gb; }
-  } else if (MODE == WROW_SUM) {
-    float acc = 0.f;
-    for (int b = l; b < B; b += 64) acc += row[b];
-    acc = rc_wave_sum(acc);
-    if (l == 0) gr[out_off + j] = acc;
-  } else {
-    float acc = 0.f;
-    for (int b = l; b < B; b += 64) acc = fmaf(row[b], v[b], acc);
-    acc = rc_wave_sum(acc);
-    if (l == 0) gr[j] = acc;
-  }
-}
+// row passes (k_wrows, the gradient record, w_dims_ok): csrc/rcmarl_wide_rows.h
 
 // b1, b2, W3, b3 -= lr * grad (masked agents only); loss_out[s][n] = sum(diff^2)/B
 __global__ __launch_bounds__(256) void k_wsmall_sgd(const float* __restrict__ grads, const float* __restrict__ losspart,
@@ -796,10 +744,6 @@ __global__ __launch_bounds__(256) void k_wactor_small_adam(const float* __restri
   }
 }
 
-static inline bool w_dims_ok(int S, int N, int B, int K, int J, int ldp, int ldb) {
-  return S > 0 && N > 0 && B > 0 && K > 0 && J > 0 && ldp > 0 && ldb >= B;
-}
-
 }  // namespace
 
 RCMARL_EXPORT int rcmarl_wide_grad_size(int hid) { return w_grad_size(hid); }
@@ -902,7 +846,7 @@ RCMARL_EXPORT int rcmarl_wide_head_fit(float* a2, const float* theta, const floa
   RCMARL_LAUNCH(k_whead_fit_cols, gc, block, 0, stream, (const float*)a2, theta, y, dz3, losspart, N, B, in_dim, hid,
                 ldp, ldb, nchunk);
   RCMARL_LAUNCH((k_wrows<WROW_FIT>), gr, block, 0, stream, a2, (const float*)dz3, theta, (const int*)nullptr, grads, 0,
-                N, B, in_dim, hid, ldp, ldb);
+                N, B, in_dim, hid, ldp, ldb, (const int*)nullptr);
   return rcmarl_check_launch();
 }
 
@@ -912,7 +856,8 @@ RCMARL_EXPORT int rcmarl_wide_bias_grad(const float* dz1, float* grads, int S, i
   if (!dz1 || !grads || S <= 0 || N <= 0 || B <= 0 || hid <= 0 || ldb < B) return RCMARL_ERR_ARG;
   const dim3 gr(rc_ceil_div(hid, 4), N, S), block(256);
   RCMARL_LAUNCH((k_wrows<WROW_SUM>), gr, block, 0, stream, const_cast<float*>(dz1), (const float*)nullptr,
-                (const float*)nullptr, (const int*)nullptr, grads, 2 * hid + 1, N, B, 0, hid, 0, ldb);
+                (const float*)nullptr, (const int*)nullptr, grads, 2 * hid + 1, N, B, 0, hid, 0, ldb,
+                (const int*)nullptr);
   return rcmarl_check_launch();
 }
 
@@ -965,7 +910,7 @@ static int wide_consensus_head_impl(const float* phi, const float* nparts, int n
                     stream, (const float*)est, phi, nparts, n_parts, coop, ebuf, agg_out, N, B, hid, ldb, d, H);
   }
   RCMARL_LAUNCH((k_wrows<WROW_DOT>), dim3(rc_ceil_div(hid + 1, 4), N, S), block, 0, stream, const_cast<float*>(phi),
-                (const float*)ebuf, (const float*)nullptr, coop, grads, 0, N, B, in_dim, hid, ldp, ldb);
+                (const float*)ebuf, (const float*)nullptr, coop, grads, 0, N, B, in_dim, hid, ldp, ldb, (const int*)nullptr);
   return rcmarl_check_launch();
 }
 

@@ -70,7 +70,7 @@ class EngineConfig:
                  n_states=2, max_ep_len=20, n_ep_fixed=50, n_epochs=10, buffer_size=2000, common_reward=False,
                  nrow=5, ncol=5, n_seeds=1, rng_mode="device", mu=0.1, scaling=True, randomize_state=True,
                  local_fit_steps=5, lattice="auto", critic_hid=HID, actor_hid=HID, tr_hid=HID, adv_wide2="auto",
-                 w1_tiled="auto", fit_from_live="auto", clip_report=False, adv_actor="refuse"):
+                 w1_tiled="auto", fit_from_live="auto", clip_report=False, adv_actor="refuse", ragged_wide="refuse"):
         self.n_agents, self.agent_label = int(n_agents), list(agent_label)
         self.in_nodes = [list(map(int, row)) for row in in_nodes]
         self.gamma, self.slow_lr, self.fast_lr = float(gamma), float(slow_lr), float(fast_lr)
@@ -103,6 +103,12 @@ class EngineConfig:
         if adv_actor not in ("refuse", "auto", "launch", "loop"):
             raise ValueError("adv_actor must be 'refuse', 'auto', 'launch' or 'loop'")
         self.adv_actor = adv_actor
+        # nets of another width than 20 on an irregular communication graph (or per-agent H): "refuse" (the combination raises below) |
+        # "auto" (the critic-family heads take the fused ragged kernel, rcmarl_wide_consensus_head_ragged; the wide actor never reads
+        # the graph and simply runs)
+        if ragged_wide not in ("refuse", "auto"):
+            raise ValueError("ragged_wide must be 'refuse' or 'auto'")
+        self.ragged_wide = ragged_wide
         # local fits of the 20-unit nets on the lattice path: the fp32 W1 of the message lives in accumulator-tile order between the
         # SGD steps of a fit (rcmarl_layer1_backward_sgd_lattice_tiled): "auto" (see W1_TILED_AUTO) | True | False
         if not any(w1_tiled is v for v in (True, False)) and w1_tiled != "auto":
@@ -148,20 +154,22 @@ class EngineConfig:
             raise ValueError("actor_hid must be positive")
         if self.tr_hid < 1:
             raise ValueError("tr_hid must be positive")
+        refuse_ragged = not self.regular and self.ragged_wide == "refuse"
+        hint = "; ragged_wide='auto' runs wide nets on an irregular graph (the fused ragged head, csrc/wide_head_ragged.hip)"
         if self.actor_hid != HID:
             if self.adv_actor == "refuse" and any(lab != COOP for lab in self.agent_label):
                 raise ValueError("a wide actor (actor_hid = %d) needs an all-cooperative team: the Greedy / Malicious / Faulty agents' "
                                  "mini-batch chains (csrc/minibatch_fit.hip) are compiled for 20 units (adv_actor='auto' routes their "
                                  "actor fits to the wide-actor kernels)" % self.actor_hid)
-            if not self.regular:
-                raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit actor (actor_hid = %d)"
-                                 % self.actor_hid)
-        if not self.regular and self.critic_hid != HID:
+            if refuse_ragged:
+                raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit actor (actor_hid = %d)%s"
+                                 % (self.actor_hid, hint))
+        if refuse_ragged and self.critic_hid != HID:
             raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit critic: the wide head's gather / "
-                             "GEMM / select chain is sized by one d (critic_hid = %d)" % self.critic_hid)
-        if not self.regular and self.tr_hid != HID:
+                             "GEMM / select chain is sized by one d (critic_hid = %d)%s" % (self.critic_hid, hint))
+        if refuse_ragged and self.tr_hid != HID:
             raise ValueError("an irregular communication graph (or per-agent H) needs the 20-unit team-reward net: the wide head's "
-                             "gather / GEMM / select chain is sized by one d (tr_hid = %d)" % self.tr_hid)
+                             "gather / GEMM / select chain is sized by one d (tr_hid = %d)%s" % (self.tr_hid, hint))
 
     @property
     def d(self):
@@ -269,6 +277,11 @@ class RPBCACEngine:
             self.order = torch.tensor(np.asarray(order, dtype=np.int32), **i32)
             self.classes = classes                                   # [(d, H, first, count)]
             self.class_table = (capi.RaggedClass * max(1, len(classes)))(*[capi.RaggedClass(*k) for k in classes])
+            for k in ("critic", "tr"):
+                dmax = max([k_[0] for k_ in classes], default=1)
+                if self.hid[k] != HID and not lib.rcmarl_wide_consensus_head_ragged_supported(self.hid[k], dmax):
+                    raise ValueError("the fused ragged head (rcmarl_wide_consensus_head_ragged) does not take in-neighbourhoods of %d "
+                                     "with a %d-unit %s net: beyond its LDS tile" % (dmax, self.hid[k], k))
         # circulant in-graph (the reference's own pattern, main.py:28) with d = 2H+2: K1 shares one selection
         # network among consecutive agents (rcmarl_consensus_params_circulant; RCMARL_K1_CIRC=0 disables)
         circ = c.regular and all(row == [(i + k) % N for k in range(c.d)] for i, row in enumerate(c.in_nodes))
@@ -369,8 +382,11 @@ class RPBCACEngine:
         self.w_dz3, self.w_ebuf, self.w_v = (torch.zeros(S, N, self.ldb, **f32) for _ in range(3))
         self.w_grads = torch.zeros(S, N, L.rcmarl_wide_grad_size(hid), **f32)
         self.w_losspart = torch.zeros(S, N, (self.cap + L.rcmarl_wide_rows_per_chunk() - 1) // L.rcmarl_wide_rows_per_chunk(), **f32)
-        self.w_hmat, self.w_hb = torch.zeros(S, N, d + 1, hid, **f32), torch.zeros(S, N, d + 1, **f32)
-        self.w_est = torch.zeros(S, N, d + 1, self.ldb, **f32)
+        if self.cfg.regular:
+            self.w_hmat, self.w_hb = torch.zeros(S, N, d + 1, hid, **f32), torch.zeros(S, N, d + 1, **f32)
+            self.w_est = torch.zeros(S, N, d + 1, self.ldb, **f32)
+        else:                                 # irregular graph: the fused head (rcmarl_wide_consensus_head_ragged) needs none of them
+            self.w_hmat = self.w_hb = self.w_est = None
         self._init_wide_actor()
 
     def _init_wide_actor(self):
@@ -577,7 +593,16 @@ class RPBCACEngine:
             self._wide_forward_pk(xkey, self.theta[net], net, B, "net", want_a2=True)
         else:
             self._wide_forward(xkey, self.theta[net], net, B, a1=self.a1net[net])
-        if pk:      # |phi|^2 per row came out of the forward's epilogue
+        if not c.regular:
+            # irregular graph / per-agent H: gather + skinny GEMM + selection + residual in one kernel per 32 classes, no scratch sized
+            # by d; |phi|^2 from the packed forward's parts where that ran, else accumulated in the kernel's own pass over phi
+            if self.classes:
+                L.rcmarl_wide_consensus_head_ragged(self.w_a2.data_ptr(), self.pk.npart.data_ptr() if pk else None,
+                                                    L.rcmarl_pk_parts(hid) if pk else 0, self.theta[net].data_ptr(), msg_all.data_ptr(),
+                                                    self.nbr_off.data_ptr(), self.nbr_idx.data_ptr(), self.order.data_ptr(),
+                                                    self.class_table, len(self.classes), self.w_ebuf.data_ptr(), self.w_grads.data_ptr(),
+                                                    None, None, 0, S, N, B, self.in_dim[net], hid, self.ldp[net], self.ldb, self.stream)
+        elif pk:    # |phi|^2 per row came out of the forward's epilogue
             L.rcmarl_wide_consensus_head_nrm(self.w_a2.data_ptr(), self.pk.npart.data_ptr(), L.rcmarl_pk_parts(hid), self.theta[net].data_ptr(),
                                              msg_all.data_ptr(), self.nbr.data_ptr(), self.coop.data_ptr(), self.w_hmat.data_ptr(),
                                              self.w_hb.data_ptr(), self.w_est.data_ptr(), self.w_ebuf.data_ptr(), self.w_grads.data_ptr(),
@@ -708,7 +733,8 @@ class RPBCACEngine:
         for name in ("w_a1", "w_a2", "w_dz1"):
             swap_attr(name, units)
         for name in ("w_dz3", "w_ebuf", "w_v", "w_grads", "w_losspart", "w_hmat", "w_hb", "w_est"):
-            swap_attr(name, rows)
+            if getattr(self, name) is not None:          # (the head's scratch exists on a regular graph only; sharding needs one)
+                swap_attr(name, rows)
         swap_attr("coop", lambda t: t[a0:a1])
         swap_attr("nbr", lambda t: t[a0:a1])
         families = [("critic", hid, ("s", "ns"), self.in_c)] + ([("tr", HID, ("sa",), self.in_r)] if sh.shard_tr else [])

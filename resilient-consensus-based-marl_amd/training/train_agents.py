@@ -16,6 +16,8 @@ Extra (optional) ``args`` keys on top of the reference's (main.py:26-44):
              then carries ``attrs['clip_report']`` = {net: {below, above, steps, P_hid, in_nodes, sender_rate}} of the run
   adv_actor  'auto' (default) | 'launch' | 'loop' | 'refuse': how Greedy / Malicious / Faulty agents' actor fits run when the
              models' actors are wider than 20 units (EngineConfig.adv_actor)
+  ragged_wide  'auto' (default) | 'refuse': models of another width than 20 units on ragged ``in_nodes`` or with agents of differing
+             H run (the critic-family heads on the fused ragged kernel) or are refused (EngineConfig.ragged_wide)
 """
 import numpy as np
 import pandas as pd
@@ -54,7 +56,7 @@ def train_RPBCAC(env, agents, args, exp_buffer=None, engine_hook=None):
                        ncol=env.ncol, n_seeds=1, rng_mode=args.get('rng_mode', 'numpy'),
                        scaling=bool(getattr(env, 'scaling', not np.isscalar(env.mean_state))),
                        randomize_state=env.randomize_state, clip_report=_truthy(args.get('clip_report')),
-                       adv_actor=args.get('adv_actor', 'auto'))
+                       adv_actor=args.get('adv_actor', 'auto'), ragged_wide=args.get('ragged_wide', 'auto'))
     lib, device = engine_hook if engine_hook is not None else (None, "cuda")
     eng = RPBCACEngine(cfg, seeds=[int(args.get('random_seed', 0))], device=device, lib=lib)
     # ---- agents -> stacked parameter matrices
